@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the sort/scan hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR (N = 1): after the timed steps, the sorted keys (or the scan)
+of the last one go to DIR/*.npy as float64, a fixed sample of 2^22 positions
+for larger outputs; the inputs come from --seed, so two builds can be compared
+output for output.
 
 Metric (BASELINE.json): Mkeys/s sorting 2^28 uint32 keys with satradix
 (radix = 16, the reference's default: 4-bit digits), key order bit-exact vs the
@@ -104,7 +109,17 @@ def parse_args(argv=None):
     ap.add_argument("--watchdog", type=float, default=900.0,
                     help="N > 1: seconds a rank may spend in one leg before it ends itself with exit code 3 (a stuck collective)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / exchange-plan test on CPU (gloo); not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write what the last timed step computed to DIR/<name>.npy (float64; a fixed, seeded sample "
+                         "of at most 2^22 values when the output is larger), so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is for single-GPU runs (--gpus 1)")
+    return args
 
 
 WORKLOADS = {
@@ -130,6 +145,32 @@ def make_input(workload, n, seed):
     if workload == "scan":  # clo_scan_bench.c:219-223: values in [0,128)
         return rng.integers(0, 128, n, dtype=np.uint32)
     raise ValueError(workload)
+
+
+DUMP_VALUES = 1 << 22    # float64 values over all files of --dump-outputs: 32 MiB
+DUMP_SEED = 20261015     # the sampled positions: the same in every run and every build
+
+
+def dump_outputs(dump_dir, workload, got):
+    """Writes the result a caller of the timed path receives (`got`: the sorted array, or the scan) to
+    dump_dir/<name>.npy as float64, which holds every 32-bit value exactly: uint32 results as they are, 64-bit
+    elements as their two 32-bit words (pairs: keys and values). Outputs larger than DUMP_VALUES are sampled at
+    DUMP_SEED's positions, in ascending order. Returns what the JSON line says about the dump."""
+    names = {"scan": ["scan"], "satradix_pairs": ["keys", "values"], "satradix_u64": ["keys_hi", "keys_lo"]}.get(workload, ["keys"])
+    m = DUMP_VALUES // len(names)
+    idx = None
+    if got.size > m:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(got.size, m, replace=False))
+        got = got[idx]
+    if got.dtype == np.uint64:
+        words = [got >> np.uint64(32), got & np.uint64(0xFFFFFFFF)]
+    else:
+        words = [got]
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, w in zip(names, words):
+        np.save(os.path.join(dump_dir, name + ".npy"), w.astype(np.float64))
+    return {"dir": dump_dir, "files": [n + ".npy" for n in names], "dtype": "float64", "values_per_file": int(got.size),
+            "sample": None if idx is None else {"seed": DUMP_SEED, "positions": int(idx.size)}}
 
 
 def reference_bitonic_round_trips(log2n):
@@ -546,6 +587,8 @@ def _run_sharded_leg(be, etype, n_local, steps, warmup, seed, rank, world, local
 def main_sharded(args, world, rank, local_rank):
     if args.workload not in ("satradix_u32", "satradix_u64"):
         raise SystemExit("multi-GPU runs shard the satradix key sorts only; %s is replicas-only" % args.workload)
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs is for single-GPU runs")
     os.environ.setdefault("CLO_NO_WARMUP", "1")
     be = _Backend(args.dry_run, local_rank)
     etype = WORKLOADS[args.workload][1]
@@ -613,11 +656,11 @@ def kernel_sources_sha16(group):
     return h.hexdigest()[:16]
 
 
-def single_leg(workload, log2n, steps, warmup, radix, seed, cpu_sample_log2n=None, with_cpu=True):
+def single_leg(workload, log2n, steps, warmup, radix, seed, cpu_sample_log2n=None, with_cpu=True, dump_dir=None):
     """One workload on cuda:0 through the C API: PREWARM + warmup untimed steps, exactly `steps` timed ones between
     fences, then the same number again with every kernel bracketed by HIP events (roofline + live guard), a
-    size-independent correctness check of what was timed, and the CPU oracle on a bounded sample. Returns the
-    full line as a dict."""
+    size-independent correctness check of what was timed, and the CPU oracle on a bounded sample. With `dump_dir`,
+    the last timed step's result goes there (dump_outputs). Returns the full line as a dict."""
     import torch
     import cl_ops_amd as clo
     from cl_ops_amd import _hip
@@ -671,6 +714,12 @@ def single_leg(workload, log2n, steps, warmup, radix, seed, cpu_sample_log2n=Non
     fence()
     wall = time.perf_counter() - t0
     dev_ms = timer.elapsed_ms()
+    # what the last timed step computed, kept on the device before anything runs again; it goes to the host after the
+    # roofline leg (a host pause here would let the clocks drop before that leg)
+    last = None
+    if dump_dir:
+        last = dst.clone()
+        torch.cuda.synchronize()
 
     # ---- roofline leg: the same K steps again with every kernel launch
     # bracketed by HIP events on its own stream (clo_hip_timing_*). Kept out of
@@ -682,6 +731,8 @@ def single_leg(workload, log2n, steps, warmup, radix, seed, cpu_sample_log2n=Non
         step()
     fence()
     lib.clo_hip_timing_enable(0)
+    dump = dump_outputs(dump_dir, workload, last.cpu().numpy().view(host.dtype)) if dump_dir else None
+    del last
 
     # ---- correctness of what was timed (size-independent properties) ----
     got = dst.cpu().numpy().view(host.dtype)
@@ -797,6 +848,8 @@ def single_leg(workload, log2n, steps, warmup, radix, seed, cpu_sample_log2n=Non
                    "api": "clo_sort_with_device_data" if workload != "scan" else "clo_scan_with_device_data"},
         "correct": ok, "device_ms_per_step": round(dev_ms / steps, 4), "roofline": roof, "live_guard": guard,
     }
+    if dump:
+        out["dump_outputs"] = dump
     for x in (op, bsrc, bdst, q, ctx):
         x.close()
     del src, dst
@@ -895,7 +948,8 @@ def main_single(args):
     torch.cuda.set_device(0)
     workload = args.workload
     log2n = args.log2n or WORKLOADS[workload][0]
-    out = single_leg(workload, log2n, args.steps, args.warmup, args.radix, args.seed, args.cpu_sample_log2n, not args.no_cpu_baseline)
+    out = single_leg(workload, log2n, args.steps, args.warmup, args.radix, args.seed, args.cpu_sample_log2n, not args.no_cpu_baseline,
+                     args.dump_outputs)
     ok = out["correct"]
     if not out["live_guard"]["ok"]:
         sys.stderr.write("bench.py: live guard: %r\n" % (out["live_guard"],))

@@ -69,6 +69,62 @@ def test_reference_round_trip_yardstick():
     assert bench.contract_bytes_per_elem("sbitonic", 16, 16) == 8 * 136
 
 
+def test_dump_outputs_are_exact_float64_within_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    small = np.sort(bench.make_input("satradix_u32", 5000, 1))
+    d = bench.dump_outputs(str(tmp_path / "u32"), "satradix_u32", small)
+    got = np.load(tmp_path / "u32" / "keys.npy")
+    assert d["files"] == ["keys.npy"] and d["sample"] is None
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), small)
+    # larger than the budget: the same seeded positions every time, both 32-bit words of every sampled pair exact
+    pairs = np.sort(bench.make_input("satradix_pairs", 3 << 20, 2))
+    for sub in ("a", "b"):
+        d = bench.dump_outputs(str(tmp_path / sub), "satradix_pairs", pairs)
+    assert d["files"] == ["keys.npy", "values.npy"] and d["sample"]["positions"] == bench.DUMP_VALUES // 2
+    k, v = (np.load(tmp_path / "a" / f) for f in d["files"])
+    assert np.array_equal(k, np.load(tmp_path / "b" / "keys.npy")) and np.array_equal(v, np.load(tmp_path / "b" / "values.npy"))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(pairs.size, bench.DUMP_VALUES // 2, replace=False))
+    assert np.array_equal(k, (pairs[idx] >> np.uint64(32)).astype(np.float64))
+    assert np.array_equal(v, (pairs[idx] & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "x"]])
+def test_bench_refuses_bad_arguments(argv):
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(argv)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload,log2n", [("satradix_u32", 16), ("satradix_pairs", 22)])
+def test_bench_dumps_what_the_timed_steps_computed(tmp_path, workload, log2n):
+    """`--steps K` times exactly K steps and the line says so; --dump-outputs writes the last one's result, which is
+    numpy's (stable) sort of the seeded input — at every sampled position when the output exceeds the budget."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", workload,
+                        "--log2n", str(log2n), "--seed", "5", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, env=env, timeout=600)
+    d = _line(p)
+    assert d["correct"] is True and d["steps"] == 3 and d["ms_per_step"] > 0
+    host = bench.make_input(workload, 1 << log2n, 5)
+    if workload == "satradix_pairs":
+        want = host[np.argsort(host >> np.uint64(32), kind="stable")]
+        idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(want.size, bench.DUMP_VALUES // 2, replace=False))
+        assert d["dump_outputs"]["sample"]["positions"] == idx.size
+        assert np.array_equal(np.load(tmp_path / "keys.npy"), (want[idx] >> np.uint64(32)).astype(np.float64))
+        assert np.array_equal(np.load(tmp_path / "values.npy"), (want[idx] & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    else:
+        assert d["dump_outputs"]["sample"] is None
+        assert np.array_equal(np.load(tmp_path / "keys.npy"), np.sort(host).astype(np.float64))
+
+
 def test_watchdog_ends_a_stuck_rank_with_a_nonzero_exit():
     """A leg that takes longer than --watchdog seconds (here: any leg, the limit is 50 ms) ends the rank with
     exit code 3 — a plain exit of a fresh child process — and the launcher reports failure instead of hanging."""
