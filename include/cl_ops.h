@@ -1,6 +1,6 @@
 /*
  * cl_ops.h — aggregate public header (reference: src/cl_ops/cl_ops.h:33-48),
- * restricted to the sort/scan hot path this library implements.
+ * with the three modules of upstream: sort, scan and rng.
  */
 #ifndef CL_OPS_H
 #define CL_OPS_H
@@ -9,6 +9,7 @@
 #include "clo_ccl.h"
 #include "clo_scan.h"
 #include "clo_sort.h"
+#include "clo_rng.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

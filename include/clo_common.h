@@ -51,6 +51,7 @@ typedef enum {
 
 typedef struct clo_sort CloSort;
 typedef struct clo_scan CloScan;
+typedef struct clo_rng CloRng;
 
 /* clo_common.in.h:139-165 */
 const char* clo_type_get_name(CloType type);

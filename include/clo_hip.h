@@ -388,6 +388,26 @@ size_t clo_hip_kernel_lds_bytes(const char* family, int elem_size, int param);
  * compile-time-schedule kernels on 2^14-element tiles — 2^13 of 8 bytes — above), tiled = 0 one launch per step (0). */
 size_t clo_hip_bitonic_lds_bytes(size_t numel, int elem_size, int tiled);
 
+/* ---- CloRng (include/clo_rng.h; upstream: rng/clo_rng.c, rng/clo_rng_*.cl) ----
+ * gen: the generator's place in CLO_RNG_IMPLS (0 lcg, 1 xorshift64, 2 xorshift128, 3 mwc64x, 4 parkmiller,
+ * 5 tauslcg); `states`: device memory of `count` states of that generator's seed size.
+ * clo_hip_rng_device_source: the text of include/clo_rng/clo_rng_device.hpp, fixed when the library was built.
+ * clo_hip_rng_init: states[g] = from_ulong(hash(g + main_seed)) for g < count (clo_rng_init.cl); hash 0 none,
+ * 1 KNUTH, 2 XS1. Asynchronous on `stream`.
+ * clo_hip_rng_init_jit: the same with `hash` the body of #define CLO_RNG_HASH(x), compiled with hiprtc; returns when
+ * the kernel has run. CLO_HIP_EARGS with the compiler's log in *log (malloc'd; the caller frees it) when the hash
+ * does not compile.
+ * clo_hip_rng_fill: out[i] = f(draw i / count of state i % count) for i < numel, f(x) = x >> (32 - bits), or
+ * x % maxint when maxint != 0 (bits 1..32 either way); the states advance by their number of draws. One launch,
+ * asynchronous on `stream`. layout: 0 the library's choice (one state per lane), 1 one state per lane, 4 four
+ * consecutive states per lane, one 16-byte store per draw (count % 4 == 0 and `out` 16-byte aligned, else
+ * CLO_HIP_EARGS; measured slower, for comparison). */
+const char* clo_hip_rng_device_source(void);
+int clo_hip_rng_init(int gen, void* states, size_t count, uint64_t main_seed, int hash, void* stream);
+int clo_hip_rng_init_jit(int gen, const char* hash, void* states, size_t count, uint64_t main_seed, void* stream, char** log);
+int clo_hip_rng_fill(int gen, void* states, size_t count, unsigned* out, size_t numel, unsigned bits, unsigned maxint,
+	int layout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
