@@ -112,6 +112,8 @@ _sig("clo_sort_new", vp, C.c_char_p, C.c_char_p, vp, C.POINTER(ci), C.POINTER(ci
 _sig("clo_sort_destroy", None, vp)
 _sig("clo_sort_with_device_data", vp, vp, vp, vp, vp, vp, sz, sz, _E)
 _sig("clo_sort_with_host_data", _u32, vp, vp, vp, vp, vp, sz, sz, _E)
+_sig("clo_sort_by_key_with_device_data", vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, _E)
+_sig("clo_sort_by_key_with_host_data", _u32, vp, vp, vp, vp, vp, vp, vp, sz, sz, _E)
 _sig("clo_sort_get_context", vp, vp)
 _sig("clo_sort_get_program", vp, vp)
 _sig("clo_sort_get_element_type", ci, vp)
@@ -370,6 +372,38 @@ class Sorter:
         if not ok:
             raise CloError("clo", CLO_ERROR_LIBRARY, "clo_sort_with_host_data failed")
         return out
+
+    def by_key_with_device_data(self, q_exec, keys_in, values_in, keys_out, values_out, numel, lws_max=0, q_comm=None):
+        """clo_sort_by_key_with_device_data: stable sort of keys_in carrying 4-byte values along (satradix).
+        values_in None: the values are the indices 0 .. numel - 1 (argsort); keys_out None: no keys are written."""
+        err = _Err()
+        h = lambda b: b.h if b is not None else None
+        evt = lib.clo_sort_by_key_with_device_data(self.h, q_exec.h, h(q_comm), h(keys_in), h(values_in), h(keys_out),
+                                                   h(values_out), numel, lws_max, err.ref)
+        err.raise_if_set()
+        return evt
+
+    def by_key_with_host_data(self, keys, values=None, q_exec=None, q_comm=None, lws_max=0):
+        """clo_sort_by_key_with_host_data: (keys sorted, values carried along) as numpy arrays; values None gives
+        the stable argsort (uint32) as the second array."""
+        k = np.ascontiguousarray(keys)
+        if k.ndim != 1 or k.itemsize != self.element_size:
+            raise ValueError("keys: a 1-D array of %d-byte elements" % self.element_size)
+        v = None
+        if values is not None:
+            v = np.ascontiguousarray(values)
+            if v.shape != k.shape or v.itemsize != 4:
+                raise ValueError("values: 4-byte elements, as many as keys")
+        ko = np.empty_like(k)
+        vo = np.empty_like(v) if v is not None else np.empty(k.shape, dtype=np.uint32)
+        err = _Err()
+        ok = lib.clo_sort_by_key_with_host_data(self.h, q_exec.h if q_exec else None, q_comm.h if q_comm else None,
+                                                k.ctypes.data_as(vp), v.ctypes.data_as(vp) if v is not None else None,
+                                                ko.ctypes.data_as(vp), vo.ctypes.data_as(vp), k.size, lws_max, err.ref)
+        err.raise_if_set()
+        if not ok:
+            raise CloError("clo", CLO_ERROR_LIBRARY, "clo_sort_by_key_with_host_data failed")
+        return ko, vo
 
     def key_spec(self):
         """(elem_size, key_size, key_shift, key_bits, key_kind, descending) as parsed from

@@ -141,6 +141,11 @@ typedef struct {
 		const void* src2_dev, const int* piece_source,
 		int key_shift, int key_bits, int* result_in_b, int* handled, GError** err);
 	cl_bool (*reserve_segments)(struct clo_sort* sorter, CCLQueue* cq_exec, size_t numel, int nseg, int* handled, GError** err);
+	/* sort_by_key: clo_sort_by_key_with_device_data (include/clo_sort.h) once clo_sort_abstract.c has checked what every
+	 * by-key sort refuses (the sorter, its element size, a run-time compiled get_key, values_out, numel). NULL: this sorter
+	 * has none. values_in / keys_out may be NULL. */
+	CCLEvent* (*sort_by_key)(struct clo_sort* sorter, CCLQueue* cq_exec, CCLBuffer* keys_in, CCLBuffer* values_in, CCLBuffer* keys_out,
+		CCLBuffer* values_out, size_t numel, GError** err);
 } clo_sort_impl_ext;
 CLO_INTERNAL const clo_sort_impl_ext* clo_sort_impl_ext_find(const char* name);
 CLO_INTERNAL extern const clo_sort_impl_ext clo_sort_satradix_ext;

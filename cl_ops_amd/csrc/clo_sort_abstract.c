@@ -467,6 +467,108 @@ finish:
 	return status;
 }
 
+/* ---- sorting by key (not upstream; include/clo_sort.h) ---- */
+
+/* Why a by-key sort refuses these arguments, or NULL: checked before any device call. */
+static const char* by_key_refusal(CloSort* sorter, const void* keys_in, const void* values_out, size_t numel,
+	const clo_sort_impl_ext** ext) {
+	*ext = clo_sort_impl_ext_find(sorter->impl_def.name);
+	if (!*ext || !(*ext)->sort_by_key) return "sorting by key is provided by the satradix sorter only";
+	if (sorter->jit) return "sorting by key needs a get_key of the ahead-of-time family, not one compiled at run time";
+	if (sorter->spec.elem_size > 4) return "sorting by key takes elements of 1, 2 or 4 bytes (8-byte ones would need 12-byte pairs)";
+	if (!keys_in) return "keys_in is required";
+	if (!values_out) return "values_out is required";
+	if (numel > 0xffffffffull) return "numel must be below 2^32";
+	return NULL;
+}
+
+CCLEvent* clo_sort_by_key_with_device_data(CloSort* sorter, CCLQueue* cq_exec, CCLQueue* cq_comm,
+	CCLBuffer* keys_in, CCLBuffer* values_in, CCLBuffer* keys_out, CCLBuffer* values_out,
+	size_t numel, size_t lws_max, GError** err) {
+	clo_return_val_if_fail(sorter != NULL, NULL);
+	clo_return_val_if_fail(err == NULL || *err == NULL, NULL);
+	(void) cq_comm;  /* nothing is copied: the first pass reads the arrays where they are */
+	(void) lws_max;
+	const clo_sort_impl_ext* ext;
+	const char* why = by_key_refusal(sorter, keys_in, values_out, numel, &ext);
+	if (why) {
+		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "%s", why);
+		return NULL;
+	}
+	clo_return_val_if_fail(cq_exec != NULL, NULL);
+	return ext->sort_by_key(sorter, cq_exec, keys_in, values_in, keys_out, values_out, numel, err);
+}
+
+/* Upstream's blocking host-data path (sort/clo_sort_abstract.c:348-395) for the four arrays: copy in on cq_comm, sort on
+ * cq_exec, copy out on cq_comm. */
+cl_bool clo_sort_by_key_with_host_data(CloSort* sorter, CCLQueue* cq_exec, CCLQueue* cq_comm,
+	const void* keys_in, const void* values_in, void* keys_out, void* values_out,
+	size_t numel, size_t lws_max, GError** err) {
+	clo_return_val_if_fail(sorter != NULL, CL_FALSE);
+	clo_return_val_if_fail(err == NULL || *err == NULL, CL_FALSE);
+	const clo_sort_impl_ext* ext;
+	const char* why = by_key_refusal(sorter, keys_in, values_out, numel, &ext);
+	if (why) {
+		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "%s", why);
+		return CL_FALSE;
+	}
+	if (numel == 0) return CL_TRUE;
+
+	cl_bool status = CL_FALSE;
+	CCLBuffer* dev[4] = { NULL, NULL, NULL, NULL };   /* keys in, values in, keys out, values out */
+	CCLQueue* intern_queue = NULL;
+	CCLEvent* evt = NULL;
+	CCLEventWaitList ewl = NULL;
+	GError* err_internal = NULL;
+	const size_t kbytes = numel * (size_t) sorter->spec.elem_size, vbytes = numel * sizeof(cl_uint);
+	const size_t bytes[4] = { kbytes, vbytes, kbytes, vbytes };
+	const int used[4] = { 1, values_in != NULL, keys_out != NULL, 1 };
+	CCLContext* ctx = sorter->ctx;
+
+	if (cq_exec == NULL) {
+		CCLDevice* d = ccl_context_get_device(ctx, 0, &err_internal);
+		if (err_internal) goto error_handler;
+		intern_queue = ccl_queue_new(ctx, d, 0, &err_internal);
+		if (err_internal) goto error_handler;
+		cq_exec = intern_queue;
+	}
+	if (cq_comm == NULL) cq_comm = cq_exec;
+	for (int i = 0; i < 4; ++i) {
+		if (!used[i]) continue;
+		dev[i] = ccl_buffer_new(ctx, CL_MEM_READ_WRITE, bytes[i], NULL, &err_internal);
+		if (err_internal) goto error_handler;
+	}
+	ccl_buffer_enqueue_write(dev[0], cq_comm, CL_TRUE, 0, kbytes, (void*) keys_in, NULL, &err_internal);
+	if (err_internal) goto error_handler;
+	if (values_in) {
+		ccl_buffer_enqueue_write(dev[1], cq_comm, CL_TRUE, 0, vbytes, (void*) values_in, NULL, &err_internal);
+		if (err_internal) goto error_handler;
+	}
+	evt = clo_sort_by_key_with_device_data(sorter, cq_exec, cq_comm, dev[0], dev[1], dev[2], dev[3], numel, lws_max, &err_internal);
+	if (err_internal) goto error_handler;
+	evt = ccl_buffer_enqueue_read(dev[3], cq_comm, CL_FALSE, 0, vbytes, values_out, evt ? ccl_ewl(&ewl, evt, NULL) : NULL, &err_internal);
+	if (err_internal) goto error_handler;
+	if (keys_out) {
+		evt = ccl_buffer_enqueue_read(dev[2], cq_comm, CL_FALSE, 0, kbytes, keys_out, NULL, &err_internal);
+		if (err_internal) goto error_handler;
+	}
+	ccl_event_wait(ccl_ewl(&ewl, evt, NULL), &err_internal);
+	if (err_internal) goto error_handler;
+	if (ext->check_status && !ext->check_status(sorter, cq_exec, &err_internal)) goto error_handler;
+	status = CL_TRUE;
+	goto finish;
+
+error_handler:
+	clo_gerror_propagate(err, err_internal);
+	status = CL_FALSE;
+
+finish:
+	ccl_event_wait_list_clear(&ewl);
+	for (int i = 0; i < 4; ++i) if (dev[i]) ccl_buffer_destroy(dev[i]);
+	if (intern_queue) ccl_queue_destroy(intern_queue);
+	return status;
+}
+
 /* ---- getters, ref: clo_sort_abstract.c:428-629 ---- */
 
 CCLContext* clo_sort_get_context(CloSort* sorter) {

@@ -61,21 +61,28 @@ static CloScan* clo_sort_satradix_get_scanner(CloSort* sorter, GError** err) {
 	return data->scanner;
 }
 
+static int satradix_reserve_as(CloSort* sorter, CCLQueue* cq_exec, size_t numel, int es, int key_bits, int pairs, GError** err);
+
 /* The cached buffers for a sort of `numel` elements on cq_exec: the ping-pong partner, the
  * workspace (its header cleared when the allocation is fresh), the status word watched by the
  * queue when the sort's kernels poll. Before the command's start event, so that (re)allocation
  * is not timed as device work. The cached buffers belong to one queue at a time. */
 static int satradix_reserve(CloSort* sorter, CCLQueue* cq_exec, size_t numel, GError** err) {
-	clo_sort_satradix_data* data = (clo_sort_satradix_data*) clo_sort_get_data(sorter);
 	const CloSortKeySpec* ks = clo_sort_get_key_spec(sorter);
+	const int jit = clo_sort_get_jit(sorter) != NULL;   /* then (key, index) pairs of 8 bytes are what gets sorted */
+	return satradix_reserve_as(sorter, cq_exec, numel, jit ? 8 : ks->elem_size, jit ? 32 : ks->key_bits, jit, err);
+}
+
+/* The same for a sort of `numel` elements of `es` bytes by `key_bits` key bits; `pairs`: the pair buffer too (numel x 8). */
+static int satradix_reserve_as(CloSort* sorter, CCLQueue* cq_exec, size_t numel, int es, int key_bits, int pairs, GError** err) {
+	clo_sort_satradix_data* data = (clo_sort_satradix_data*) clo_sort_get_data(sorter);
 	const int bits_in_digit = (int) clo_tzc((int) data->radix);
 	void* stream = ccl_queue_get_stream(cq_exec);
 	if (clo_hip_failed(clo_stream_guard_enter(&data->guard, cq_exec), err, "hipStreamWaitEvent")) return 0;
-	const int jit = clo_sort_get_jit(sorter) != NULL;   /* then (key, index) pairs of 8 bytes are what gets sorted */
-	const size_t ws_bytes = clo_hip_radix_workspace_bytes(numel, jit ? 8 : ks->elem_size, jit ? 32 : ks->key_bits, bits_in_digit);
-	if (clo_hip_failed(clo_devbuf_reserve(&data->tmp, jit ? numel * 8 : numel * (size_t) ks->elem_size), err, "hipMalloc(satradix aux)")) return 0;
+	const size_t ws_bytes = clo_hip_radix_workspace_bytes(numel, es, key_bits, bits_in_digit);
+	if (clo_hip_failed(clo_devbuf_reserve(&data->tmp, numel * (size_t) es), err, "hipMalloc(satradix aux)")) return 0;
 	if (clo_hip_failed(clo_devbuf_reserve(&data->workspace, ws_bytes), err, "hipMalloc(satradix workspace)")) return 0;
-	if (jit && clo_hip_failed(clo_devbuf_reserve(&data->pairs, numel * 8), err, "hipMalloc(satradix key pairs)")) return 0;
+	if (pairs && clo_hip_failed(clo_devbuf_reserve(&data->pairs, numel * 8), err, "hipMalloc(satradix key pairs)")) return 0;
 	if (data->ws_ready != data->workspace.ptr || data->ws_ready_bytes != data->workspace.bytes) {   /* a fresh allocation: its status word is garbage */
 		if (clo_hip_failed(clo_hip_memset_async(data->workspace.ptr, 0, 512, stream), err, "hipMemsetAsync")) return 0;
 		data->ws_ready = data->workspace.ptr;
@@ -84,7 +91,7 @@ static int satradix_reserve(CloSort* sorter, CCLQueue* cq_exec, size_t numel, GE
 	/* the queues that watch this sorter's status word must never be left with the
 	 * address of a workspace that has been reallocated since */
 	clo_status_cell_set_word(data->status, data->workspace.ptr);
-	if (clo_hip_radix_polls(numel, jit ? 8 : ks->elem_size, bits_in_digit)) {
+	if (clo_hip_radix_polls(numel, es, bits_in_digit)) {
 		/* tile-to-tile look-back inside the passes: a give-up must not pass as success */
 		if (clo_status_cell_take_tripped(data->status)) clo_debug("SATRADIX: the previous sort on this sorter gave up a spin");
 		ccl_queue_watch_status(cq_exec, data->status);
@@ -170,6 +177,70 @@ static CCLEvent* clo_sort_satradix_sort_with_device_data(CloSort* sorter, CCLQue
 		}
 	}
 
+	if (per_kernel) {
+		GError* e2 = NULL;
+		CCLEvent* last = clo_kernel_events_remove(&ke, &e2);
+		if (e2) { clo_gerror_propagate(err, e2); return NULL; }
+		if (last) return last;
+		evt = ccl_queue_begin_command(cq_exec, CLO_SORT_SATRADIX_KNAME_SCATTER, err);   /* (no launch was observed) */
+		if (!evt) return NULL;
+	}
+	if (!ccl_queue_end_command(cq_exec, evt, err)) { ccl_queue_abort_command(cq_exec, evt); return NULL; }
+	return evt;
+}
+
+/* clo_sort_by_key_with_device_data (include/clo_sort.h; clo_sort_abstract.c has refused what every by-key sort refuses).
+ * The pairs (element << 32 | value) are what is sorted, in the two cached pair buffers `pairs` and `tmp`; where the chain-free
+ * radix-16 / 256 passes take the sort, its first pass reads keys_in and values_in and its last one writes keys_out and
+ * values_out (clo_hip_radix_sort_kv). A profiling queue gets one event per kernel, named as the plain sort's. */
+static CCLEvent* clo_sort_satradix_sort_by_key(CloSort* sorter, CCLQueue* cq_exec, CCLBuffer* keys_in, CCLBuffer* values_in,
+	CCLBuffer* keys_out, CCLBuffer* values_out, size_t numel, GError** err) {
+	clo_sort_satradix_data* data = (clo_sort_satradix_data*) clo_sort_get_data(sorter);
+	const CloSortKeySpec* ks = clo_sort_get_key_spec(sorter);
+	const int bits_in_digit = (int) clo_tzc((int) data->radix);
+	const size_t kbytes = numel * (size_t) ks->elem_size, vbytes = numel * 4;
+	CCLEvent* evt = NULL;
+
+	if (ks->key_kind == 2 && ks->key_bits != 8 * ks->key_size) {
+		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "satradix: a floating-point key must span its whole type");
+		return NULL;
+	}
+	const int key_kind = (ks->key_kind == 1 && ks->key_bits < 8 * ks->key_size) ? 0 : ks->key_kind;  /* sign bit masked off */
+	if (kbytes > ccl_buffer_get_size(keys_in) || (keys_out && kbytes > ccl_buffer_get_size(keys_out))
+		|| (values_in && vbytes > ccl_buffer_get_size(values_in)) || vbytes > ccl_buffer_get_size(values_out)) {
+		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "numel (%zu) exceeds the size of the device buffers", numel);
+		return NULL;
+	}
+	clo_debug("SATRADIX: by key, radix=%u, numel=%zu, key bits [%d,%d), values %s, keys out %s", data->radix, numel,
+		ks->key_shift, ks->key_shift + ks->key_bits, values_in ? "given" : "indices", keys_out ? "written" : "not written");
+
+	if (numel > 0 && !satradix_reserve_as(sorter, cq_exec, numel, 8, ks->key_bits, 1, err)) return NULL;
+
+	static const clo_kname knames[] = {
+		{ "radix_hist", CLO_SORT_SATRADIX_KNAME_HISTOGRAM }, { "radix_ghist", CLO_SORT_SATRADIX_KNAME_HISTOGRAM },
+		{ "radix_offsets", "clo_scan_blelloch_wgscan" },
+		{ "radix_pass", CLO_SORT_SATRADIX_KNAME_SCATTER }, { "radix_sweep", CLO_SORT_SATRADIX_KNAME_SCATTER },
+		{ "radix_small", CLO_SORT_SATRADIX_KNAME_LOCALSORT },
+		{ "radix_kv_pack", "satradix_kv_pack" }, { "radix_kv_unpack", "satradix_kv_unpack" }
+	};
+	const int per_kernel = ccl_queue_is_profiling(cq_exec) && numel > 0;
+	clo_kernel_events ke;
+	if (per_kernel) {
+		clo_kernel_events_install(&ke, cq_exec, knames, sizeof(knames) / sizeof(knames[0]), CLO_SORT_SATRADIX_KNAME_SCATTER);
+	} else {
+		evt = ccl_queue_begin_command(cq_exec, CLO_SORT_SATRADIX_KNAME_SCATTER, err);
+		if (!evt) return NULL;
+	}
+	if (numel > 0) {
+		const int st = clo_hip_radix_sort_kv(ccl_buffer_get_device_ptr(keys_in), values_in ? ccl_buffer_get_device_ptr(values_in) : NULL,
+			keys_out ? ccl_buffer_get_device_ptr(keys_out) : NULL, ccl_buffer_get_device_ptr(values_out), data->pairs.ptr, data->tmp.ptr,
+			numel, ks->elem_size, ks->key_shift, ks->key_bits, key_kind, bits_in_digit, data->workspace.ptr, data->workspace.bytes,
+			ccl_queue_get_stream(cq_exec));
+		if (clo_hip_failed(st, err, "clo_hip_radix_sort_kv")) {
+			if (per_kernel) clo_kernel_events_remove(&ke, NULL); else ccl_queue_abort_command(cq_exec, evt);
+			return NULL;
+		}
+	}
 	if (per_kernel) {
 		GError* e2 = NULL;
 		CCLEvent* last = clo_kernel_events_remove(&ke, &e2);
@@ -594,7 +665,7 @@ static CCLEvent* clo_sort_satradix_sort_segments(CloSort* sorter, CCLQueue* cq_e
 }
 
 const clo_sort_impl_ext clo_sort_satradix_ext = { "satradix", clo_sort_satradix_check_status, clo_sort_satradix_host_pipeline,
-	clo_sort_satradix_reserve, clo_sort_satradix_sort_segments, clo_sort_satradix_reserve_segments };
+	clo_sort_satradix_reserve, clo_sort_satradix_sort_segments, clo_sort_satradix_reserve_segments, clo_sort_satradix_sort_by_key };
 
 typedef struct {
 	clo_sort_satradix_data* data;

@@ -73,9 +73,22 @@ inline clo_keyx clo_keyx_make(int kind, int key_shift, int key_bits) {
 	return k;
 }
 
+// The arrays of a key-value sort (clo_hip_radix_sort_kv): what it sorts are 8-byte pairs (element << 32 | value).
+// keys_in: the elements (1, 2 or 4 bytes); values_in: 4-byte words, null = the element's index (argsort);
+// keys_out: null = not written; values_out: always written.
+struct clo_kv_io {
+	const void* keys_in;
+	const unsigned* values_in;
+	void* keys_out;
+	unsigned* values_out;
+};
+
 // Radix passes (clo_hip_radix4.hip) and their histogram / counter-scan steps
 // (clo_hip_radixw.hip).
 size_t clo_radix4_workspace_bytes(size_t n, int elem_size, int digit_bits, int key_bits);
+// key_shift: of the key field inside the PAIR (32 + its shift inside the element); kx made for that field
+int clo_radix4_sort_kv(const clo_kv_io& io, void* pairs_a, void* pairs_b, size_t n, int key_size, int key_shift,
+	int key_bits, int digit_bits, clo_keyx kx, void* ws, hipStream_t s);
 size_t clo_radix4_partition_workspace_bytes(size_t n, int elem_size, int bits);
 int clo_radix4_partition(const void* src, void* dst, size_t n, int elem_size, unsigned shift, int bits,
 	unsigned long long* counts, void* ws, hipStream_t s);
@@ -99,6 +112,10 @@ size_t clo_radixw_lds_bytes(int digit_bits);
 // the hand-off words of the scan that follows it on the stream (clo_radixw_launch_offsets), which returns in *dbase the row
 // of digit bases the pass kernel adds to toff[tile][digit] (null: toff is final)
 int clo_radixw_launch_tilehist(const void* in, size_t n, int elem_size, int bits, unsigned shift, unsigned mask,
+	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s);
+// The first histogram of a key-value sort: the 8-byte pairs' tiles, read from the key array alone (key_size bytes
+// per element; the pair's key field lies at `shift` inside element << 32). bits = 8 (radix 16 / 256) only.
+int clo_radixw_launch_tilehist_kv(const void* keys, size_t n, int key_size, int bits, unsigned shift, unsigned mask,
 	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s);
 int clo_radixw_launch_tilehist_bytes(const unsigned char* dig, size_t n, int elem_size, int bits, unsigned mask,
 	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, hipStream_t s);

@@ -102,6 +102,31 @@ int clo_hip_radix_sort_fed(const void* src, void* dst, void* tmp, size_t numel,
 	return clo_radix4_sort(src, dst, tmp, numel, elem_size, key_shift, key_bits, digit_bits, kx, first_digits, workspace, s);
 }
 
+size_t clo_hip_radix_kv_workspace_bytes(size_t numel, int key_size, int key_bits, int digit_bits) {
+	if (key_size != 1 && key_size != 2 && key_size != 4) return 0;
+	return clo_hip_radix_workspace_bytes(numel, 8, key_bits, digit_bits);   // (the pair sort's: same tiles, same passes)
+}
+
+int clo_hip_radix_sort_kv(const void* keys_in, const void* values_in, void* keys_out, void* values_out, void* pairs_a, void* pairs_b,
+	size_t numel, int key_size, int key_shift, int key_bits, int key_kind, int digit_bits,
+	void* workspace, size_t workspace_bytes, void* stream) {
+	if (numel == 0) return 0;
+	if (!keys_in || !values_out || !pairs_a || !pairs_b || pairs_a == pairs_b || !workspace) return CLO_HIP_EARGS;
+	const void* arrays[4] = { keys_in, values_in, keys_out, values_out };
+	for (int i = 0; i < 4; ++i) if (arrays[i] == pairs_a || arrays[i] == pairs_b) return CLO_HIP_EARGS;
+	if (key_size != 1 && key_size != 2 && key_size != 4) return CLO_HIP_EUNSUPPORTED;
+	if (key_bits < 1 || key_shift < 0 || key_shift + key_bits > 8 * key_size) return CLO_HIP_EARGS;
+	if (key_kind < 0 || key_kind > 2) return CLO_HIP_EARGS;
+	if (key_kind == 2 && key_bits != 16 && key_bits != 32) return CLO_HIP_EARGS;
+	if (digit_bits < 1 || digit_bits > 8) return CLO_HIP_EUNSUPPORTED;
+	if (numel > 0xffffffffull) return CLO_HIP_EARGS;
+	if (workspace_bytes < clo_hip_radix_kv_workspace_bytes(numel, key_size, key_bits, digit_bits)) return CLO_HIP_EWORKSPACE;
+	const clo_kv_io io = { keys_in, (const unsigned*) values_in, keys_out, (unsigned*) values_out };
+	// the key field inside the pair (element << 32 | value)
+	const clo_keyx kx = clo_keyx_make(key_kind, 32 + key_shift, key_bits);
+	return clo_radix4_sort_kv(io, pairs_a, pairs_b, numel, key_size, 32 + key_shift, key_bits, digit_bits, kx, workspace, (hipStream_t) stream);
+}
+
 int clo_hip_radix_preload(void) { return clo_radixw_preload(); }
 
 size_t clo_hip_radix_seg_workspace_bytes(size_t numel, int nseg, int elem_size, int digit_bits) {

@@ -33,6 +33,49 @@
 namespace {
 
 // ---------------------------------------------------------------------------
+// Key-value sorts (clo_hip_radix_sort_kv): the pairs (key << 32 | value) are composed where the first pass loads its
+// tile and split where the last pass stores it, so that no pack or unpack step goes through HBM on its own.
+// ---------------------------------------------------------------------------
+template <int KB> struct kv_key;
+template <> struct kv_key<1> { typedef uint8_t type; };
+template <> struct kv_key<2> { typedef uint16_t type; };
+template <> struct kv_key<4> { typedef uint32_t type; };
+
+// ITEMS consecutive pairs from element `at` on, `valid` of which exist (the others become 0). `aligned`: both arrays
+// start 16-byte aligned (a thread's keys and values are then vector loads).
+template <int KB, int ITEMS>
+__device__ __forceinline__ void kv_load_pairs(const clo_kv_io& kv, size_t at, unsigned valid, bool aligned, uint64_t (&pair)[ITEMS]) {
+	typedef typename kv_key<KB>::type K;
+	const K* kp = reinterpret_cast<const K*>(kv.keys_in) + at;
+	K k[ITEMS];
+	unsigned v[ITEMS];
+	if (valid == (unsigned) ITEMS) {
+		load_blocked<K, ITEMS>(kp, k, aligned);
+		if (kv.values_in) {   // (the same for the whole launch)
+			load_blocked<unsigned, ITEMS>(kv.values_in + at, v, aligned);
+		} else {
+			#pragma unroll
+			for (int i = 0; i < ITEMS; ++i) v[i] = (unsigned) at + (unsigned) i;   // (argsort: indices are below 2^32)
+		}
+	} else {
+		#pragma unroll
+		for (int i = 0; i < ITEMS; ++i) {
+			k[i] = (unsigned) i < valid ? kp[i] : (K) 0;
+			v[i] = (unsigned) i < valid ? (kv.values_in ? kv.values_in[at + i] : (unsigned) at + (unsigned) i) : 0u;
+		}
+	}
+	#pragma unroll
+	for (int i = 0; i < ITEMS; ++i) pair[i] = ((uint64_t) k[i] << 32) | v[i];
+}
+
+template <int KB>
+__device__ __forceinline__ void kv_store_pair(const clo_kv_io& kv, unsigned gi, uint64_t e) {
+	typedef typename kv_key<KB>::type K;
+	if (kv.keys_out) reinterpret_cast<K*>(kv.keys_out)[gi] = (K) (e >> 32);   // (the same for the whole launch)
+	kv.values_out[gi] = (unsigned) e;
+}
+
+// ---------------------------------------------------------------------------
 // The pass kernel: two digit steps per trip through HBM.
 //
 // A tile is split by digit `lo` and then by digit `hi` inside the work-group
@@ -54,14 +97,20 @@ namespace {
 // instead of n elements (clo_radixw_launch_tilehist_bytes).
 // SEG: a segmented launch (clo_hip_radix_sort_segmented): `n` is the number of TILES of the launch, `tdesc` says which
 // segment a tile belongs to and where it lies; positions, offsets and the row of digit bases are the segment's own.
-template <typename E, int LB, int HB, bool BIG, bool DIG = false, bool SEG = false>
+// KV_IN / KV_OUT: the first / last pass of a key-value sort (clo_hip_radix_sort_kv), E = the 8-byte pair key << 32 | value,
+// the key being of KV_IN / KV_OUT bytes (0: an ordinary pass). KV_IN: the tile is read from the two arrays of `kv`
+// (keys_in, and values_in or — null — the global index) and composed in registers; `in` is not read and `aligned` speaks
+// of both arrays. KV_OUT: the scatter splits every pair, the key to kv.keys_out (null: not written) and the value to
+// kv.values_out; `out` is not written.
+template <typename E, int LB, int HB, bool BIG, bool DIG = false, bool SEG = false, int KV_IN = 0, int KV_OUT = 0>
 __global__ __launch_bounds__((pair_shape<E, BIG>::THREADS), (pair_shape<E, BIG>::THREADS >= 1024 ? 8 : 6))   // 3 work-groups per CU (LDS): 6 waves per SIMD, <= 80 VGPRs (59 used); BIG: 2 x 16 waves, <= 64
 void clo_radix4_pair_kernel(const E* __restrict__ in, E* __restrict__ out, size_t n,
 	unsigned shift, unsigned mask_lo, unsigned mask_hi,
 	const unsigned* __restrict__ thist, const unsigned* __restrict__ toff, const unsigned* __restrict__ dbase,
 	const unsigned* __restrict__ tinfo, int aligned,
 	clo_keyx kx_in, clo_keyx kx_out, unsigned char* __restrict__ dig_out = nullptr, unsigned next_shift = 0,
-	const clo_seg_tile* __restrict__ tdesc = nullptr, const E* __restrict__ in2 = nullptr) {
+	const clo_seg_tile* __restrict__ tdesc = nullptr, const E* __restrict__ in2 = nullptr, clo_kv_io kv = clo_kv_io()) {
+	static_assert((KV_IN == 0 && KV_OUT == 0) || (sizeof(E) == 8 && !SEG), "key-value passes: 8-byte pairs, one array");
 
 	constexpr int THREADS = pair_shape<E, BIG>::THREADS;
 	constexpr int ITEMS = pair_shape<E, BIG>::ITEMS;
@@ -117,7 +166,9 @@ void clo_radix4_pair_kernel(const E* __restrict__ in, E* __restrict__ out, size_
 		if (dbase) goff += dbase[tid];   // (the one-launch counter scan keeps the digit bases in a row of their own)
 	}
 	E key[ITEMS];
-	if (full) {
+	if constexpr (KV_IN != 0) {
+		kv_load_pairs<KV_IN, ITEMS>(kv, base + tbase, full ? (unsigned) ITEMS : (count > tbase ? count - tbase : 0u), aligned != 0, key);
+	} else if (full) {
 		if constexpr (SEG) load_blocked_unaligned<E, ITEMS>(in + base + tbase, key);   // (a segment starts at any element)
 		else load_blocked<E, ITEMS>(in + base + tbase, key, aligned != 0);
 	} else {
@@ -221,7 +272,8 @@ void clo_radix4_pair_kernel(const E* __restrict__ in, E* __restrict__ out, size_
 						#pragma unroll
 						for (int k = 0; k < VEC; ++k) vo[k] = clo_keyx_inv<E>(v[k], kx_out);
 					}
-					*reinterpret_cast<vecE_u*>(&out[gi0]) = vo;
+					if constexpr (KV_OUT != 0) kv_store_pair<KV_OUT>(kv, gi0, vo[0]);   // (VEC = 1: one pair)
+					else *reinterpret_cast<vecE_u*>(&out[gi0]) = vo;
 					if constexpr (DIG) {
 						if constexpr (VEC == 4) {
 							typedef unsigned u32_u __attribute__((aligned(1)));
@@ -241,7 +293,8 @@ void clo_radix4_pair_kernel(const E* __restrict__ in, E* __restrict__ out, size_
 					for (int k = 0; k < VEC; ++k) {
 						const unsigned gi = p + k + s_delta[pc_digit<E>(v[k], shift, mask2, nbits2)];
 						if (gi < n32) {
-							out[gi] = KX ? clo_keyx_inv<E>(v[k], kx_out) : v[k];
+							if constexpr (KV_OUT != 0) kv_store_pair<KV_OUT>(kv, gi, KX ? clo_keyx_inv<E>(v[k], kx_out) : v[k]);
+							else out[gi] = KX ? clo_keyx_inv<E>(v[k], kx_out) : v[k];
 							if constexpr (DIG) dig_out[gi] = (unsigned char) (v[k] >> next_shift);
 						}
 					}
@@ -253,7 +306,8 @@ void clo_radix4_pair_kernel(const E* __restrict__ in, E* __restrict__ out, size_
 						const E e = s_stage[p + k];
 						const unsigned gi = p + k + s_delta[pc_digit<E>(e, shift, mask2, nbits2)];
 						if (gi < n32) {
-							out[gi] = KX ? clo_keyx_inv<E>(e, kx_out) : e;
+							if constexpr (KV_OUT != 0) kv_store_pair<KV_OUT>(kv, gi, KX ? clo_keyx_inv<E>(e, kx_out) : e);
+							else out[gi] = KX ? clo_keyx_inv<E>(e, kx_out) : e;
 							if constexpr (DIG) dig_out[gi] = (unsigned char) (e >> next_shift);
 						}
 					}
@@ -669,6 +723,162 @@ int small_dispatch(const void* src, void* dst, size_t n, int key_shift, int key_
 	return (int) hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Key-value sorts on the other paths (the one-launch kernel, the single-sweep passes, radix other than 16 / 256):
+// the pairs are packed into a buffer of their own, sorted by the pair sort as it is, and unpacked. Four elements per
+// thread, coalesced; grid-stride, so any n < 2^32.
+// ---------------------------------------------------------------------------
+constexpr int KV_PACK_THREADS = 256;
+
+template <typename K>
+__global__ __launch_bounds__(KV_PACK_THREADS)
+void clo_radix_kv_pack_kernel(const K* __restrict__ keys, const unsigned* __restrict__ values, uint64_t* __restrict__ pairs, size_t n) {
+	for (size_t i = (size_t) blockIdx.x * KV_PACK_THREADS + threadIdx.x; i < n; i += (size_t) gridDim.x * KV_PACK_THREADS)
+		pairs[i] = ((uint64_t) keys[i] << 32) | (values ? values[i] : (unsigned) i);
+}
+
+template <typename K>
+__global__ __launch_bounds__(KV_PACK_THREADS)
+void clo_radix_kv_unpack_kernel(const uint64_t* __restrict__ pairs, K* __restrict__ keys, unsigned* __restrict__ values, size_t n) {
+	for (size_t i = (size_t) blockIdx.x * KV_PACK_THREADS + threadIdx.x; i < n; i += (size_t) gridDim.x * KV_PACK_THREADS) {
+		const uint64_t e = pairs[i];
+		if (keys) keys[i] = (K) (e >> 32);
+		values[i] = (unsigned) e;
+	}
+}
+
+unsigned kv_pack_grid(size_t n) {
+	const size_t g = (n + KV_PACK_THREADS - 1) / KV_PACK_THREADS;
+	return (unsigned) (g < 8192 ? (g ? g : 1) : 8192);
+}
+
+int kv_pack(const clo_kv_io& io, uint64_t* pairs, size_t n, int key_size, hipStream_t s) {
+	clo_timing_scope timing("radix_kv_pack", s);
+	#define CLO_KVP(K) hipLaunchKernelGGL((clo_radix_kv_pack_kernel<K>), dim3(kv_pack_grid(n)), dim3(KV_PACK_THREADS), 0, s, (const K*) io.keys_in, io.values_in, pairs, n)
+	switch (key_size) {
+		case 1: CLO_KVP(uint8_t); break;
+		case 2: CLO_KVP(uint16_t); break;
+		case 4: CLO_KVP(uint32_t); break;
+		default: return CLO_HIP_EUNSUPPORTED;
+	}
+	#undef CLO_KVP
+	return (int) hipGetLastError();
+}
+
+int kv_unpack(const uint64_t* pairs, const clo_kv_io& io, size_t n, int key_size, hipStream_t s) {
+	clo_timing_scope timing("radix_kv_unpack", s);
+	#define CLO_KVU(K) hipLaunchKernelGGL((clo_radix_kv_unpack_kernel<K>), dim3(kv_pack_grid(n)), dim3(KV_PACK_THREADS), 0, s, pairs, (K*) io.keys_out, io.values_out, n)
+	switch (key_size) {
+		case 1: CLO_KVU(uint8_t); break;
+		case 2: CLO_KVU(uint16_t); break;
+		case 4: CLO_KVU(uint32_t); break;
+		default: return CLO_HIP_EUNSUPPORTED;
+	}
+	#undef CLO_KVU
+	return (int) hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Key-value sorts (clo_hip_radix_sort_kv), host side.
+//
+// The chain-free passes of radix 16 / 256 (LB = HB = 4): the first pass and its histogram read the two arrays, the
+// last pass writes them, the passes in between are the 8-byte pair passes as they are. Bytes per element for 32-bit
+// keys and values: histogram 4 (keys only), first pass 8 in + 8 out, middle passes 16 each (+ the digit stream), last
+// pass 8 + 8 — the AoS pair sort's traffic, less half of its first histogram.
+// ---------------------------------------------------------------------------
+template <int KB, bool BIG, bool DIG, int KVI, int KVO>
+void kv_launch_pass(const uint64_t* in, uint64_t* out, size_t n, unsigned tiles, unsigned shift, unsigned mask_lo, unsigned mask_hi,
+	const unsigned* thist, const unsigned* toff, const unsigned* dbase, const unsigned* tinfo, int aligned, clo_keyx kin, clo_keyx kout,
+	unsigned char* dig, unsigned next_shift, const clo_kv_io& io, hipStream_t s) {
+	hipLaunchKernelGGL((clo_radix4_pair_kernel<uint64_t, 4, 4, BIG, DIG, false, KVI, KVO>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<uint64_t, BIG>::THREADS), 0, s,
+		in, out, n, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned, kin, kout, dig, next_shift, (const clo_seg_tile*) nullptr, (const uint64_t*) nullptr, io);
+}
+
+template <int KB, bool BIG>
+void kv_launch(bool first, bool last, bool dig, const uint64_t* in, uint64_t* out, size_t n, unsigned tiles, unsigned shift, unsigned mask_lo, unsigned mask_hi,
+	const unsigned* thist, const unsigned* toff, const unsigned* dbase, const unsigned* tinfo, int aligned, clo_keyx kin, clo_keyx kout,
+	unsigned char* dig_out, unsigned next_shift, const clo_kv_io& io, hipStream_t s) {
+	#define CLO_KVL(D, I, O) kv_launch_pass<KB, BIG, D, I, O>(in, out, n, tiles, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned, kin, kout, dig_out, next_shift, io, s)
+	if (first && last) CLO_KVL(false, KB, KB);
+	else if (last) CLO_KVL(false, 0, KB);
+	else if (first && BIG && dig) CLO_KVL(BIG, KB, 0);   // (the digit stream goes with the big tiles)
+	else if (first) CLO_KVL(false, KB, 0);
+	#undef CLO_KVL
+}
+
+template <int KB>
+int rp_sort_kv_impl(const clo_kv_io& io, uint64_t* pa, uint64_t* pb, size_t n, int key_shift, int key_bits, clo_keyx kx, void* ws, hipStream_t s) {
+	constexpr int LB = 4, HB = 4, PB = 8;
+	typedef uint64_t E;
+	const int passes = (key_bits + PB - 1) / PB;
+	const rp_layout L = rp_make_layout(n, (int) sizeof(E), PB);
+	unsigned* thist = (unsigned*) ((char*) ws + L.thist);
+	unsigned* toff = (unsigned*) ((char*) ws + L.toff);
+	unsigned* partial = (unsigned*) ((char*) ws + L.partial);
+	unsigned* tinfo = (unsigned*) ((char*) ws + L.tinfo);
+	const unsigned tiles = (unsigned) L.tiles;
+	const bool big = clo_radix_big_tiles(n, (int) sizeof(E));
+	unsigned char* dig = (L.dig != 0 && passes > 1 && !clo_hip_env()->no_digits) ? (unsigned char*) ws + L.dig : nullptr;
+	const clo_keyx kx_none = { 0, 0, 0 };
+	// One pass that reads and writes the caller's arrays cannot run in place (other tiles' results land on keys
+	// this tile has not read yet): it writes the pairs, and the unpack kernel splits them.
+	const bool split_after = passes == 1 && (io.keys_out == io.keys_in || (const void*) io.values_out == (const void*) io.values_in);
+	const bool vec_ok = (uintptr_t) io.keys_in % 16 == 0 && (uintptr_t) io.values_in % 16 == 0;
+	const E* cur_in = nullptr;
+	for (int p = 0; p < passes; ++p) {
+		const bool first = p == 0, last = p + 1 == passes && !split_after;   // last: this pass writes the caller's arrays
+		E* cur_out = last ? nullptr : (p % 2 == 0 ? pa : pb);
+		const int rem = key_bits - p * PB;
+		const int bits = rem < PB ? rem : PB;
+		const int lo_bits = bits < LB ? bits : LB, hi_bits = bits - lo_bits;
+		const unsigned shift = (unsigned) (key_shift + p * PB);
+		const unsigned mask_lo = (1u << lo_bits) - 1u, mask_hi = (1u << hi_bits) - 1u;
+		{
+			clo_timing_scope timing("radix_hist", s);
+			const int st = first
+				? clo_radixw_launch_tilehist_kv(io.keys_in, n, KB, PB, shift, (mask_hi << LB) | mask_lo, thist, tinfo, partial, tiles, big, kx, s)
+				: (dig ? clo_radixw_launch_tilehist_bytes(dig, n, (int) sizeof(E), PB, (mask_hi << LB) | mask_lo, thist, tinfo, partial, tiles, big, s)
+				       : clo_radixw_launch_tilehist(cur_in, n, (int) sizeof(E), PB, shift, (mask_hi << LB) | mask_lo, thist, tinfo, partial, tiles, big, kx_none, s));
+			if (st != 0) return st;
+		}
+		const unsigned* dbase = nullptr;
+		{
+			clo_timing_scope timing("radix_offsets", s);
+			const int st = clo_radixw_launch_offsets(PB, thist, tiles, partial, toff, &dbase, s);
+			if (st != 0) return st;
+		}
+		{
+			clo_timing_scope timing("radix_pass", s);
+			const int aligned = first ? (int) vec_ok : (int) ((uintptr_t) cur_in % 16 == 0);
+			const clo_keyx kin = first ? kx : kx_none, kout = p + 1 == passes ? kx : kx_none;
+			const unsigned next_shift = (unsigned) (key_shift + (p + 1) * PB);
+			if (!first && !last) {   // a middle pass: the pair passes as they are
+				if (big && dig)
+					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, true>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, true>::THREADS), 0, s,
+						cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout,
+						dig, next_shift);
+				else if (big)
+					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, true>::THREADS), 0, s,
+						cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout, nullptr, 0u);
+				else
+					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, false, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, false>::THREADS), 0, s,
+						cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout, nullptr, 0u);
+			} else if (big) {
+				kv_launch<KB, true>(first, last, dig != nullptr && p + 1 < passes, cur_in, cur_out, n, tiles, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned,
+					kin, kout, dig, next_shift, io, s);
+			} else {
+				kv_launch<KB, false>(first, last, false, cur_in, cur_out, n, tiles, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned,
+					kin, kout, nullptr, 0u, io, s);
+			}
+		}
+		cur_in = cur_out;
+	}
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess) return (int) e;
+	if (split_after) return kv_unpack(pa, io, n, KB, s);
+	return 0;
+}
+
 }  // namespace
 
 static size_t r4_pair_workspace_bytes(size_t n, int elem_size, int digit_bits) {
@@ -766,4 +976,25 @@ int clo_radix4_sort(const void* src, void* dst, void* tmp, size_t n, int elem_si
 		case 8: return rp_dispatch<uint64_t>(src, dst, tmp, n, key_shift, key_bits, digit_bits, kx, first_dig, ws, s);
 		default: return CLO_HIP_EUNSUPPORTED;
 	}
+}
+
+// Key-value sort: the fused passes where the chain-free radix-16 / 256 schedule takes an 8-byte sort of n elements,
+// otherwise pack -> the pair sort in place in pairs_a (pairs_b its partner) -> unpack.
+int clo_radix4_sort_kv(const clo_kv_io& io, void* pairs_a, void* pairs_b, size_t n, int key_size, int key_shift,
+	int key_bits, int digit_bits, clo_keyx kx, void* ws, hipStream_t s) {
+	uint64_t* pa = (uint64_t*) pairs_a;
+	uint64_t* pb = (uint64_t*) pairs_b;
+	const bool small = n <= (size_t) small_big<uint64_t>::TILE && digit_bits <= 4;   // (clo_radix4_sort's one-launch case)
+	if ((digit_bits == 4 || digit_bits == 8) && !small && !clo_radix1_applies(n, 8, digit_bits)) {
+		switch (key_size) {
+			case 1: return rp_sort_kv_impl<1>(io, pa, pb, n, key_shift, key_bits, kx, ws, s);
+			case 2: return rp_sort_kv_impl<2>(io, pa, pb, n, key_shift, key_bits, kx, ws, s);
+			case 4: return rp_sort_kv_impl<4>(io, pa, pb, n, key_shift, key_bits, kx, ws, s);
+			default: return CLO_HIP_EUNSUPPORTED;
+		}
+	}
+	int st = kv_pack(io, pa, n, key_size, s);
+	if (st == 0) st = clo_radix4_sort(pa, pa, pb, n, 8, key_shift, key_bits, digit_bits, kx, nullptr, ws, s);
+	if (st == 0) st = kv_unpack(pa, io, n, key_size, s);
+	return st;
 }

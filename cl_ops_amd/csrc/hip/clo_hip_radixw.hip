@@ -71,21 +71,29 @@ __device__ __forceinline__ bool rw_seg_tile(const clo_seg_tile* __restrict__ tde
 // twice the key bytes in flight per thread, half the work-groups. Launched with TPW = 1: with two tiles the histogram over the
 // KEYS takes the same time (2^28 uint32: 0.222 ms either way — it reads at the 4.9 TB/s a read-only stream gets on this part;
 // profiles/r05_ab_hist_keys_two_tiles.txt), unlike the one over the digit bytes below.
-template <typename E, int BITS, bool BIG, bool SEG = false, int TPW = 1>
+// L: the type the elements are READ as. E itself, or — the first pass of a key-value sort (clo_hip_radix_sort_kv) — the
+// key array's 1-, 2- or 4-byte type: the tiles are those of the 8-byte pairs E = key << 32 | value, the digit is taken
+// from key << 32, and the values are never read.
+template <typename E, int BITS, bool BIG, bool SEG = false, int TPW = 1, typename L = E>
 __global__ __launch_bounds__((rw_shape<E, BIG>::THREADS))
-void clo_radixw_tilehist_kernel(const E* __restrict__ in, size_t n, unsigned shift, unsigned mask,
+void clo_radixw_tilehist_kernel(const L* __restrict__ in, size_t n, unsigned shift, unsigned mask,
 	unsigned* __restrict__ thist, unsigned* __restrict__ tinfo, int aligned, clo_keyx kx,
-	unsigned* __restrict__ clear, unsigned clear_words, const clo_seg_tile* __restrict__ tdesc = nullptr, const E* __restrict__ in2 = nullptr) {
+	unsigned* __restrict__ clear, unsigned clear_words, const clo_seg_tile* __restrict__ tdesc = nullptr, const L* __restrict__ in2 = nullptr) {
 	static_assert(!SEG || TPW == 1, "segmented launches: one tile per work-group");
+	static_assert(std::is_same<L, E>::value || (sizeof(E) == 8 && sizeof(L) <= 4 && !SEG), "keys of a key-value sort: 8-byte pairs");
+	const auto widen = [](L x) -> E {
+		if constexpr (std::is_same<L, E>::value) return x;
+		else return (E) x << 32;
+	};
 	constexpr int R = 1 << BITS;
 	constexpr int TILE = rw_shape<E, BIG>::TILE;
 	constexpr int RW_THREADS = rw_shape<E, BIG>::THREADS;
 	constexpr int PART = RW_THREADS / TPW;   // threads of one tile
 	constexpr int ITEMS = TILE / PART;
 	static_assert(PART % 64 == 0 && PART * TPW == RW_THREADS, "whole waves per tile");
-	constexpr int VB = ITEMS * (int) sizeof(E) >= 16 ? 16 : ITEMS * (int) sizeof(E);   // bytes per vector load
-	constexpr int VECS = ITEMS * (int) sizeof(E) / VB;
-	constexpr int PER = VB / (int) sizeof(E);
+	constexpr int VB = ITEMS * (int) sizeof(L) >= 16 ? 16 : ITEMS * (int) sizeof(L);   // bytes per vector load
+	constexpr int VECS = ITEMS * (int) sizeof(L) / VB;
+	constexpr int PER = VB / (int) sizeof(L);
 	// 32 copies of every counter, copy = lane mod 32, bin-major: the 32 lanes an LDS
 	// instruction serves together hit 32 different banks and never one address (an
 	// LDS add holds its bank for many cycles; one copy per wave, lanes colliding on
@@ -100,8 +108,8 @@ void clo_radixw_tilehist_kernel(const E* __restrict__ in, size_t n, unsigned shi
 	if constexpr (SEG) { if (rw_seg_tile(tdesc, base, count, (unsigned) TILE)) in = in2; }   // (the same for the whole work-group)
 	const unsigned tbase = ptid * ITEMS;
 	unsigned* const cnt = s_cnt + part * (R * COPIES) + (lane & (COPIES - 1));
-	typedef E vecA __attribute__((ext_vector_type(PER)));   // (`aligned`: the source is 16-byte aligned)
-	typedef E vecU __attribute__((ext_vector_type(PER), aligned(sizeof(E))));
+	typedef L vecA __attribute__((ext_vector_type(PER)));   // (`aligned`: the source is 16-byte aligned)
+	typedef L vecU __attribute__((ext_vector_type(PER), aligned(sizeof(L))));
 	typedef typename std::conditional<SEG, vecU, vecA>::type vecE;
 	const bool whole = count == (unsigned) TILE && (aligned || SEG);
 	// The keys are requested FIRST (round 5): the counters are zeroed and the barrier passed while they are on their way
@@ -126,13 +134,13 @@ void clo_radixw_tilehist_kernel(const E* __restrict__ in, size_t n, unsigned shi
 		for (int k = 0; k < VECS; ++k) {
 			#pragma unroll
 			for (int q = 0; q < PER; ++q)
-				atomicAdd(&cnt[((unsigned) (clo_keyx_fwd<E>(v[k][q], kx) >> shift) & mask) << 5], 1u);
+				atomicAdd(&cnt[((unsigned) (clo_keyx_fwd<E>(widen(v[k][q]), kx) >> shift) & mask) << 5], 1u);
 		}
 	} else {
 		#pragma unroll
 		for (int i = 0; i < ITEMS; ++i)
 			if (tbase + i < count)
-				atomicAdd(&cnt[((unsigned) (clo_keyx_fwd<E>(in[base + tbase + i], kx) >> shift) & mask) << 5], 1u);
+				atomicAdd(&cnt[((unsigned) (clo_keyx_fwd<E>(widen(in[base + tbase + i]), kx) >> shift) & mask) << 5], 1u);
 	}
 	__syncthreads();
 	for (unsigned i = tid; i < (unsigned) (TPW * R); i += RW_THREADS) {
@@ -613,6 +621,32 @@ int clo_radixw_launch_tilehist(const void* in, size_t n, int elem_size, int bits
 		case 2: return rw_launch_tilehist<uint16_t>(in, n, bits, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
 		case 4: return rw_launch_tilehist<uint32_t>(in, n, bits, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
 		case 8: return rw_launch_tilehist<uint64_t>(in, n, bits, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
+		default: return CLO_HIP_EUNSUPPORTED;
+	}
+}
+
+// The first histogram of a key-value sort: pair tiles, keys alone (one digit width: the radix-16 / 256 schedule's 8 bits).
+template <typename K>
+static int rw_launch_tilehist_kv(const void* keys, size_t n, unsigned shift, unsigned mask, unsigned* thist, unsigned* tinfo,
+	unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s) {
+	const int aligned = (int) ((uintptr_t) keys % 16 == 0);
+	const unsigned clear_words = partial ? clo_radixw_clear_words(8, tiles) : 0u;
+	if (big)
+		hipLaunchKernelGGL((clo_radixw_tilehist_kernel<uint64_t, 8, true, false, 1, K>), dim3(tiles), dim3(rw_shape<uint64_t, true>::THREADS), 0, s,
+			(const K*) keys, n, shift, mask, thist, tinfo, aligned, kx, partial, clear_words, nullptr, nullptr);
+	else
+		hipLaunchKernelGGL((clo_radixw_tilehist_kernel<uint64_t, 8, false, false, 1, K>), dim3(tiles), dim3(rw_shape<uint64_t, false>::THREADS), 0, s,
+			(const K*) keys, n, shift, mask, thist, tinfo, aligned, kx, partial, clear_words, nullptr, nullptr);
+	return (int) hipGetLastError();
+}
+
+int clo_radixw_launch_tilehist_kv(const void* keys, size_t n, int key_size, int bits, unsigned shift, unsigned mask,
+	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s) {
+	if (bits != 8) return CLO_HIP_EUNSUPPORTED;
+	switch (key_size) {
+		case 1: return rw_launch_tilehist_kv<uint8_t>(keys, n, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
+		case 2: return rw_launch_tilehist_kv<uint16_t>(keys, n, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
+		case 4: return rw_launch_tilehist_kv<uint32_t>(keys, n, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
 		default: return CLO_HIP_EUNSUPPORTED;
 	}
 }

@@ -196,6 +196,19 @@ int clo_hip_radix_takes_first_digits(size_t numel, int elem_size, int key_kind, 
 int clo_hip_radix_sort_fed(const void* src, void* dst, void* tmp, size_t numel,
 	int elem_size, int key_shift, int key_bits, int key_kind, int digit_bits, const unsigned char* first_digits,
 	void* workspace, size_t workspace_bytes, void* stream);
+/* Key-value sort (new functionality: clo_sort_by_key_with_device_data, include/clo_sort.h): the stable order of the
+ * key field as above, of `numel` elements of key_size (1, 2, 4) bytes in keys_in, carried over to 4-byte values:
+ * keys_out[j] = keys_in[order[j]], values_out[j] = values_in[order[j]]. values_in NULL: the values are 0 .. numel - 1
+ * (argsort); keys_out NULL: no keys are written; values_out is required. keys_out may equal keys_in and values_out
+ * values_in (in place). What is sorted are 8-byte pairs (element << 32 | value); pairs_a and pairs_b are scratch of
+ * numel * 8 bytes each, distinct from each other and from the four arrays. Where clo_hip_radix_sort would run the
+ * chain-free radix-16 / 256 passes on 8-byte elements, the first pass (and its histogram) reads the two arrays and
+ * the last one writes them; elsewhere a pack and an unpack kernel go around the pair sort. Its kernels poll exactly
+ * when those of an 8-byte sort do: clo_hip_radix_polls(numel, 8, digit_bits). Asynchronous on `stream`. */
+size_t clo_hip_radix_kv_workspace_bytes(size_t numel, int key_size, int key_bits, int digit_bits);
+int clo_hip_radix_sort_kv(const void* keys_in, const void* values_in, void* keys_out, void* values_out, void* pairs_a, void* pairs_b,
+	size_t numel, int key_size, int key_shift, int key_bits, int key_kind, int digit_bits,
+	void* workspace, size_t workspace_bytes, void* stream);
 /* Diagnostic: a device buffer of 8 x tiles uint64 that the LAST single-sweep pass of a sort fills with per-tile
  * s_memtime stamps (tile drawn ... stored) until it is taken away again with NULL. Process-wide, off by default. */
 int clo_hip_radix_debug_stamps(void* buffer, size_t tiles);

@@ -108,6 +108,25 @@ extern const CloSortImplDef clo_sort_satradix_def;  /* clo_sort_satradix.in.h:55
  * with CLO_SBITONIC_STEPS=1). */
 #define CLO_SORT_ABITONIC_NUM_KERNELS 26
 
+/* Not upstream. Stable ascending sort of keys_in by the sorter's key, carrying a 4-byte value along: with `order` the
+ * stable argsort of key(keys_in[i]) in satradix's order (unsigned keys by their bits, signed ones numerically, float
+ * and half keys in IEEE total order: -0 < +0, NaNs at the ends by sign), keys_out[j] = keys_in[order[j]] and
+ * values_out[j] = values_in[order[j]]. keys_in: numel elements of the sorter's element type, the key being what
+ * elem_type / key_type / get_key say (a field inside the element works). Values are opaque 4-byte words.
+ * values_in NULL: the values are 0, 1, ..., numel - 1 as uint (argsort). keys_out NULL: no keys are written.
+ * values_out is required. keys_out == keys_in and values_out == values_in (in place) are allowed. compare and
+ * lws_max are ignored, as satradix ignores them. Provided by satradix sorters with 1-, 2- or 4-byte elements and a
+ * get_key of the ahead-of-time family; anything else — the other sorters, 8-byte elements, a run-time compiled
+ * get_key, values_out NULL, numel >= 2^32 — is refused with CLO_ERROR_ARGS before any device call. Scratch: two
+ * numel x 8-byte pair buffers and the workspace, cached in the sorter. The host-data form copies in, sorts and
+ * copies out, blocking. */
+CCLEvent* clo_sort_by_key_with_device_data(CloSort* sorter, CCLQueue* cq_exec, CCLQueue* cq_comm,
+	CCLBuffer* keys_in, CCLBuffer* values_in, CCLBuffer* keys_out, CCLBuffer* values_out,
+	size_t numel, size_t lws_max, GError** err);
+cl_bool clo_sort_by_key_with_host_data(CloSort* sorter, CCLQueue* cq_exec, CCLQueue* cq_comm,
+	const void* keys_in, const void* values_in, void* keys_out, void* values_out,
+	size_t numel, size_t lws_max, GError** err);
+
 /* Not upstream — parsed form of (elem_type, key_type, compare, get_key) shared
  * by the three drivers. */
 typedef struct {
