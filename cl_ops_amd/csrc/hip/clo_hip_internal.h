@@ -107,20 +107,23 @@ int clo_bitonic_tiled_e2(void* data, size_t numel, int key_shift, int key_bits, 
 int clo_bitonic_tiled_e4(void* data, size_t numel, int key_shift, int key_bits, int key_size, int key_kind, int descending, int* launches, hipStream_t s);
 int clo_bitonic_tiled_e8(void* data, size_t numel, int key_shift, int key_bits, int key_size, int key_kind, int descending, int* launches, hipStream_t s);
 size_t clo_radixw_lds_bytes(int digit_bits);
-// tinfo: one word per tile, 1 = one bin holds the whole tile (read by the pass kernel)
+// The counters of a radix pass, in the sort's workspace:
+// thist: the tile histograms, thist[tile][digit]; toff: their scan, toff[tile][digit]
 // partial: the counter scan's workspace (clo_radixw_partial_rows(tiles) rows of 1 << bits words); the histogram launch zeroes
 // the hand-off words of the scan that follows it on the stream (clo_radixw_launch_offsets), which returns in *dbase the row
 // of digit bases the pass kernel adds to toff[tile][digit] (null: toff is final)
+// tinfo: one word per tile, 1 = one bin holds the whole tile (read by the pass kernel)
+// tiles, big: how many tiles and of which shape (clo_radix_big_tiles); segmented launches take the count from their tables
+struct clo_radix_counters { unsigned* thist; unsigned* toff; unsigned* partial; unsigned* tinfo; unsigned tiles; bool big; };
 int clo_radixw_launch_tilehist(const void* in, size_t n, int elem_size, int bits, unsigned shift, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s);
+	const clo_radix_counters& c, clo_keyx kx, hipStream_t s);
 // The first histogram of a key-value sort: the 8-byte pairs' tiles, read from the key array alone (key_size bytes
 // per element; the pair's key field lies at `shift` inside element << 32). bits = 8 (radix 16 / 256) only.
 int clo_radixw_launch_tilehist_kv(const void* keys, size_t n, int key_size, int bits, unsigned shift, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s);
+	const clo_radix_counters& c, clo_keyx kx, hipStream_t s);
 int clo_radixw_launch_tilehist_bytes(const unsigned char* dig, size_t n, int elem_size, int bits, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, hipStream_t s);
-int clo_radixw_launch_offsets(int bits, const unsigned* thist, unsigned tiles, unsigned* partial, unsigned* toff,
-	const unsigned** dbase, hipStream_t s);
+	const clo_radix_counters& c, hipStream_t s);
+int clo_radixw_launch_offsets(int bits, const clo_radix_counters& c, const unsigned** dbase, hipStream_t s);
 size_t clo_radixw_partial_rows(size_t tiles);
 
 // ---- segmented sorts (clo_hip_radix_sort_segmented): several segments of one array, each sorted on its own, in
@@ -138,12 +141,11 @@ struct clo_seg_pieces {                                                // (a ker
 };
 struct clo_seg_tables { const clo_seg_tile* tiles; const clo_seg_chunk* chunks; unsigned ntiles, nchunks, nseg; };
 int clo_radixw_launch_tilehist_seg(const void* in, const void* in2, const clo_seg_tables& sg, int elem_size, int bits, unsigned shift, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, bool big, hipStream_t s);
+	const clo_radix_counters& c, hipStream_t s);
 int clo_radixw_launch_tilehist_bytes_seg(const unsigned char* dig, const clo_seg_tables& sg, int elem_size, int bits, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, bool big, hipStream_t s);
+	const clo_radix_counters& c, hipStream_t s);
 // *dbase: nseg rows of digit bases (row = segment)
-int clo_radixw_launch_offsets_seg(int bits, const unsigned* thist, const clo_seg_tables& sg, unsigned* partial, unsigned* toff,
-	const unsigned** dbase, hipStream_t s);
+int clo_radixw_launch_offsets_seg(int bits, const clo_radix_counters& c, const clo_seg_tables& sg, const unsigned** dbase, hipStream_t s);
 size_t clo_radixw_partial_rows_seg(size_t chunks, size_t nseg);
 // pieces (npieces <= CLO_SEG_MAX, ordered by segment): lengths, first elements, segments, source (0 / 1; may be null: all 0)
 int clo_radixw_seg_build(const size_t* piece_n, const size_t* piece_base, const int* piece_seg, const int* piece_src, int npieces, int nseg, size_t tile,

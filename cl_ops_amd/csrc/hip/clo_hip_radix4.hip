@@ -375,14 +375,15 @@ void clo_radix4_small_kernel(const E* in, E* out, unsigned n, unsigned key_shift
 // Per pass: histogram of the combined digit -> counter scan -> pass kernel.
 // A requested digit width b <= 4 pairs two digits (LB = HB = b); a wider digit
 // is one pass, split in two halves.
-struct rp_layout { size_t thist, toff, partial, tinfo, dig, total, tiles; };   // dig: 0 = no digit stream; tinfo: one word per tile
+struct rp_layout { size_t thist, toff, partial, tinfo, dig, total, tiles; bool big; };   // dig: 0 = no digit stream; tinfo: one word per tile
 
 // (tiles of the shape clo_radix_big_tiles picks for n; `digits`: room for the digit stream
 // of a multi-pass sort, n bytes, where clo_radix_digit_stream says so)
 rp_layout rp_make_layout(size_t n, int elem_size, int pass_bits, bool digits = true) {
 	rp_layout L;
 	const size_t R2 = (size_t) 1 << pass_bits;
-	const size_t tile = clo_pair_tile_elems(elem_size, clo_radix_big_tiles(n, elem_size));
+	L.big = clo_radix_big_tiles(n, elem_size);
+	const size_t tile = clo_pair_tile_elems(elem_size, L.big);
 	L.tiles = (n + tile - 1) / tile;
 	if (L.tiles == 0) L.tiles = 1;
 	const size_t per = L.tiles * R2 * sizeof(unsigned);
@@ -399,27 +400,95 @@ rp_layout rp_make_layout(size_t n, int elem_size, int pass_bits, bool digits = t
 	return L;
 }
 
+// The counters of a layout (rp_layout, or rp_seg_layout with tiles = 0) in the workspace `ws`.
+template <typename Layout>
+clo_radix_counters rp_counters(void* ws, const Layout& L, size_t tiles) {
+	char* w = (char*) ws;
+	return { (unsigned*) (w + L.thist), (unsigned*) (w + L.toff), (unsigned*) (w + L.partial), (unsigned*) (w + L.tinfo), (unsigned) tiles, L.big };
+}
+
+// The digits of pass p of a sort by the key bits [key_shift, key_shift + key_bits) in passes of LB + HB bits: the low
+// digit at `shift`, the high one above it (the last pass's digits cut to the bits left), their combined mask, and
+// where the next pass's digits start.
+struct rp_digits { unsigned shift, mask_lo, mask_hi, mask, next_shift; };
+
+template <int LB, int HB>
+rp_digits rp_pass_digits(int p, int key_shift, int key_bits) {
+	constexpr int PB = LB + HB;
+	const int rem = key_bits - p * PB;
+	const int bits = rem < PB ? rem : PB;
+	const int lo_bits = bits < LB ? bits : LB, hi_bits = bits - lo_bits;
+	rp_digits d;
+	d.shift = (unsigned) (key_shift + p * PB);
+	d.mask_lo = (1u << lo_bits) - 1u;
+	d.mask_hi = (1u << hi_bits) - 1u;
+	d.mask = (d.mask_hi << LB) | d.mask_lo;
+	d.next_shift = d.shift + PB;
+	return d;
+}
+
+// The pass kernel, its run-time choices mapped onto its template switches: big tiles (c.big; 4- and 8-byte elements
+// only), the next pass's digit stream (dig_out not null; only with big tiles on the radix-16 / 256 schedule, LB = HB = 4,
+// and never out of a pass that writes a key-value sort's arrays), and, for a key-value sort of KB-byte keys, whether the
+// pass reads its two arrays (kv_in) and writes them (kv_out). Every other combination would be another set of kernels
+// to compile for sorts nobody runs. SEG: a segmented launch, n = its tiles, tdesc their table.
+template <typename E, int LB, int HB, bool SEG = false, int KB = 0>
+void rp_launch_pass(const clo_radix_counters& c, const rp_digits& d, const E* in, E* out, size_t n, const unsigned* dbase, int aligned,
+	clo_keyx kx_in, clo_keyx kx_out, unsigned char* dig_out, hipStream_t s, const clo_seg_tile* tdesc = nullptr, const E* in2 = nullptr,
+	bool kv_in = false, bool kv_out = false, const clo_kv_io& kv = clo_kv_io()) {
+	const unsigned tiles = SEG ? (unsigned) n : c.tiles;
+	const auto launch = [&](auto big, auto dig, auto kvi, auto kvo) {
+		constexpr bool BIG = decltype(big)::value, DIG = decltype(dig)::value;
+		hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, BIG, DIG, SEG, decltype(kvi)::value, decltype(kvo)::value>),
+			dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, BIG>::THREADS), 0, s,
+			in, out, n, d.shift, d.mask_lo, d.mask_hi, c.thist, c.toff, dbase, c.tinfo, aligned, kx_in, kx_out, dig_out, d.next_shift, tdesc, in2, kv);
+	};
+	const auto shape = [&](auto kvi, auto kvo) {
+		constexpr bool BIG_OK = sizeof(E) >= 4, DIG_OK = BIG_OK && LB == 4 && HB == 4 && decltype(kvo)::value == 0;
+		if constexpr (DIG_OK) {
+			if (c.big && dig_out) { launch(std::true_type(), std::true_type(), kvi, kvo); return; }
+		}
+		if constexpr (BIG_OK) {
+			if (c.big) { launch(std::true_type(), std::false_type(), kvi, kvo); return; }
+		}
+		launch(std::false_type(), std::false_type(), kvi, kvo);
+	};
+	typedef std::integral_constant<int, 0> plain;
+	typedef std::integral_constant<int, KB> key;   // (the same as `plain` when KB = 0)
+	if (kv_in && kv_out) shape(key(), key());
+	else if (kv_in) shape(key(), plain());
+	else if (kv_out) shape(plain(), key());
+	else shape(plain(), plain());
+}
+
+int kv_unpack(const uint64_t* pairs, const clo_kv_io& io, size_t n, int key_size, hipStream_t s);
+
+// The passes of a sort of `src` into `dst` (`tmp`: an array of n more elements; `src` may be `dst`).
 // first_dig (optional): the FIRST pass's combined digit of every element, one byte each, in source order, handed
 // over by whoever produced the keys (clo_hip_radix_sort_fed): the first histogram then reads n bytes instead of
 // the elements — the one re-read of the keys the sort has left.
-template <typename E, int LB, int HB>
+// KB != 0: a key-value sort of KB-byte keys (clo_hip_radix_sort_kv; E = the 8-byte pair, LB = HB = 4). The first pass
+// and its histogram read the arrays of `kv` instead of `src` (null), the last pass writes them instead of `dst`; `dst`
+// and `tmp` are two scratch pair buffers. Bytes per element for 32-bit keys and values: histogram 4 (keys only), first
+// pass 8 in + 8 out, middle passes 16 each (+ the digit stream), last pass 8 + 8 — the AoS pair sort's traffic, less
+// half of its first histogram.
+template <typename E, int LB, int HB, int KB = 0>
 int rp_sort_impl(const E* src, E* dst, E* tmp, size_t n, int key_shift, int key_bits, clo_keyx kx, const unsigned char* first_dig,
-	void* ws, hipStream_t s) {
+	const clo_kv_io& kv, void* ws, hipStream_t s) {
 	constexpr int PB = LB + HB;   // key bits per trip through HBM
 	const int passes = (key_bits + PB - 1) / PB;
 	const rp_layout L = rp_make_layout(n, (int) sizeof(E), PB);
-	unsigned* thist = (unsigned*) ((char*) ws + L.thist);
-	unsigned* toff = (unsigned*) ((char*) ws + L.toff);
-	unsigned* partial = (unsigned*) ((char*) ws + L.partial);
-	unsigned* tinfo = (unsigned*) ((char*) ws + L.tinfo);
-	const unsigned tiles = (unsigned) L.tiles;
-	const bool big = clo_radix_big_tiles(n, (int) sizeof(E));
+	const clo_radix_counters c = rp_counters(ws, L, L.tiles);
 	const bool no_dig = clo_hip_env()->no_digits != 0;   // (tests compare both)
 	// (the stream exists for the schedules of radix 16 and 256 only, LB = HB = 4: every other digit width
 	// would be another set of kernels to compile for sorts nobody times)
 	constexpr bool DIG_OK = LB == 4 && HB == 4 && sizeof(E) >= 4;
 	unsigned char* dig = (DIG_OK && L.dig != 0 && passes > 1 && !no_dig) ? (unsigned char*) ws + L.dig : nullptr;
 	const clo_keyx kx_none = { 0, 0, 0 };
+	// Key-value: one pass that reads and writes the caller's arrays cannot run in place (other tiles' results land on
+	// keys this tile has not read yet): it writes the pairs, and the unpack kernel splits them.
+	const bool split_after = KB != 0 && passes == 1 && (kv.keys_out == kv.keys_in || (const void*) kv.values_out == (const void*) kv.values_in);
+	const bool kv_aligned = (uintptr_t) kv.keys_in % 16 == 0 && (uintptr_t) kv.values_in % 16 == 0;
 
 	hipError_t e;   // (no kernel of the sort polls another work-group: the header's status word stays unused)
 
@@ -429,51 +498,28 @@ int rp_sort_impl(const E* src, E* dst, E* tmp, size_t n, int key_shift, int key_
 		E* cur_out;
 		if (inplace_odd) cur_out = (p % 2 == 0) ? tmp : dst;
 		else cur_out = ((passes - 1 - p) % 2 == 0) ? dst : tmp;
-		const int rem = key_bits - p * PB;
-		const int bits = rem < PB ? rem : PB;
-		const int lo_bits = bits < LB ? bits : LB, hi_bits = bits - lo_bits;
-		const unsigned shift = (unsigned) (key_shift + p * PB);
-		const unsigned mask_lo = (1u << lo_bits) - 1u, mask_hi = (1u << hi_bits) - 1u;
+		const bool kv_in = KB != 0 && p == 0, kv_out = KB != 0 && p + 1 == passes && !split_after;
+		const rp_digits d = rp_pass_digits<LB, HB>(p, key_shift, key_bits);
 		{
 			clo_timing_scope timing("radix_hist", s);
 			// (from the second pass on: out of the digit bytes the pass before left behind)
-			const unsigned char* hist_bytes = (dig && p > 0) ? dig : ((DIG_OK && big && p == 0 && kx.kind == 0) ? first_dig : nullptr);
-			const int st = hist_bytes
-				? clo_radixw_launch_tilehist_bytes(hist_bytes, n, (int) sizeof(E), PB, (mask_hi << LB) | mask_lo, thist, tinfo, partial, tiles, big, s)
-				: clo_radixw_launch_tilehist(cur_in, n, (int) sizeof(E), PB, shift, (mask_hi << LB) | mask_lo,
-					thist, tinfo, partial, tiles, big, p == 0 ? kx : kx_none, s);
+			const unsigned char* hist_bytes = (dig && p > 0) ? dig : ((DIG_OK && c.big && p == 0 && kx.kind == 0) ? first_dig : nullptr);
+			const int st = kv_in ? clo_radixw_launch_tilehist_kv(kv.keys_in, n, KB, PB, d.shift, d.mask, c, kx, s)
+				: hist_bytes ? clo_radixw_launch_tilehist_bytes(hist_bytes, n, (int) sizeof(E), PB, d.mask, c, s)
+				: clo_radixw_launch_tilehist(cur_in, n, (int) sizeof(E), PB, d.shift, d.mask, c, p == 0 ? kx : kx_none, s);
 			if (st != 0) return st;
 		}
 		const unsigned* dbase = nullptr;
 		{
 			clo_timing_scope timing("radix_offsets", s);
-			const int st = clo_radixw_launch_offsets(PB, thist, tiles, partial, toff, &dbase, s);
+			const int st = clo_radixw_launch_offsets(PB, c, &dbase, s);
 			if (st != 0) return st;
 		}
 		{
 			clo_timing_scope timing("radix_pass", s);
-			const int aligned = (int) ((uintptr_t) cur_in % 16 == 0);
-			const clo_keyx kin = p == 0 ? kx : kx_none, kout = p + 1 == passes ? kx : kx_none;
-			if constexpr (sizeof(E) >= 4) {
-				if (big) {
-					bool done = false;
-					if constexpr (DIG_OK) {
-						if (dig && p + 1 < passes) {
-							hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, true>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, true>::THREADS), 0, s,
-								cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout,
-								dig, (unsigned) (key_shift + (p + 1) * PB));
-							done = true;
-						}
-					}
-					if (!done)
-						hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, true>::THREADS), 0, s,
-							cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout, nullptr, 0u);
-					cur_in = cur_out;
-					continue;
-				}
-			}
-			hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, false, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, false>::THREADS), 0, s,
-				cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout, nullptr, 0u);
+			const int aligned = kv_in ? (int) kv_aligned : (int) ((uintptr_t) cur_in % 16 == 0);
+			rp_launch_pass<E, LB, HB, false, KB>(c, d, cur_in, cur_out, n, dbase, aligned, p == 0 ? kx : kx_none, p + 1 == passes ? kx : kx_none,
+				p + 1 < passes ? dig : nullptr, s, nullptr, nullptr, kv_in, kv_out, kv);
 		}
 		cur_in = cur_out;
 	}
@@ -483,13 +529,16 @@ int rp_sort_impl(const E* src, E* dst, E* tmp, size_t n, int key_shift, int key_
 		e = hipMemcpyAsync(dst, tmp, n * sizeof(E), hipMemcpyDeviceToDevice, s);
 		if (e != hipSuccess) return (int) e;
 	}
+	if constexpr (KB != 0) {
+		if (split_after) return kv_unpack(dst, kv, n, KB, s);
+	}
 	return 0;
 }
 
 template <typename E>
 int rp_dispatch(const void* src, void* dst, void* tmp, size_t n, int key_shift, int key_bits, int digit_bits,
 	clo_keyx kx, const unsigned char* first_dig, void* ws, hipStream_t s) {
-	#define CLO_RP(LB, HB) return rp_sort_impl<E, LB, HB>((const E*) src, (E*) dst, (E*) tmp, n, key_shift, key_bits, kx, first_dig, ws, s)
+	#define CLO_RP(LB, HB) return rp_sort_impl<E, LB, HB>((const E*) src, (E*) dst, (E*) tmp, n, key_shift, key_bits, kx, first_dig, clo_kv_io(), ws, s)
 	switch (digit_bits) {
 		case 1: CLO_RP(1, 1);
 		case 2: CLO_RP(2, 2);
@@ -546,34 +595,22 @@ int r4_partition_impl(const E* src, E* dst, size_t n, unsigned shift, unsigned l
 	constexpr bool TWO = BITS > 3;
 	static_assert(TWO ? PB == BITS : (LB == BITS && HB == BITS), "see above");
 	const rp_layout L = rp_make_layout(n, (int) sizeof(E), PB, false);
-	unsigned* thist = (unsigned*) ((char*) ws + L.thist);
-	unsigned* toff = (unsigned*) ((char*) ws + L.toff);
-	unsigned* partial = (unsigned*) ((char*) ws + L.partial);
-	unsigned* tinfo = (unsigned*) ((char*) ws + L.tinfo);
-	const unsigned tiles = (unsigned) L.tiles;
+	const clo_radix_counters c = rp_counters(ws, L, L.tiles);
 	const clo_keyx kx_none = { 0, 0, 0 };
 	hipError_t e = hipMemsetAsync(ws, 0, CLO_WS_HEADER_BYTES, s);   // (clo_hip_check_status may be asked about this workspace)
 	if (e != hipSuccess) return (int) e;
 	clo_timing_scope timing("msd_partition", s);
-	const bool big = clo_radix_big_tiles(n, (int) sizeof(E));
-	const unsigned mask_lo = TWO ? (1u << LB) - 1u : R - 1u, mask_hi = TWO ? (1u << HB) - 1u : 0u;
-	int st = clo_radixw_launch_tilehist(src, n, (int) sizeof(E), PB, shift, R - 1u, thist, tinfo, partial, tiles, big, kx_none, s);
+	const rp_digits d = rp_pass_digits<LB, HB>(0, (int) shift, BITS);   // (mask = R - 1)
+	int st = clo_radixw_launch_tilehist(src, n, (int) sizeof(E), PB, d.shift, d.mask, c, kx_none, s);
 	if (st != 0) return st;
 	const unsigned* dbase = nullptr;
-	st = clo_radixw_launch_offsets(PB, thist, tiles, partial, toff, &dbase, s);
+	st = clo_radixw_launch_offsets(PB, c, &dbase, s);
 	if (st != 0) return st;
 	if (counts) {
 		if (dbase) hipLaunchKernelGGL((clo_radix4_counts_from_bases_kernel<R, (1 << PB)>), dim3(1), dim3(256), 0, s, dbase, (unsigned) n, counts);
-		else hipLaunchKernelGGL((clo_radix4_counts_kernel<R, (1 << PB)>), dim3(1), dim3(256), 0, s, (const unsigned*) thist, tiles, counts);   // (one tile)
+		else hipLaunchKernelGGL((clo_radix4_counts_kernel<R, (1 << PB)>), dim3(1), dim3(256), 0, s, c.thist, c.tiles, counts);   // (one tile)
 	}
-	if (big)
-		hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, true>::THREADS), 0, s,
-			src, dst, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo,
-			(int) ((uintptr_t) src % 16 == 0), kx_none, kx_none, nullptr, 0u);
-	else
-		hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, false, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, false>::THREADS), 0, s,
-			src, dst, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo,
-			(int) ((uintptr_t) src % 16 == 0), kx_none, kx_none, nullptr, 0u);
+	rp_launch_pass<E, LB, HB>(c, d, src, dst, n, dbase, (int) ((uintptr_t) src % 16 == 0), kx_none, kx_none, nullptr, s);
 	return (int) hipGetLastError();
 }
 
@@ -621,10 +658,7 @@ int rp_sort_seg_impl(const E* src, const E* src2, E* a, E* b, size_t n, const si
 	constexpr int LB = 4, HB = 4, PB = 8;
 	const int passes = (key_bits + PB - 1) / PB;
 	const rp_seg_layout L = rp_make_seg_layout(n, nseg, (int) sizeof(E));
-	unsigned* thist = (unsigned*) ((char*) ws + L.thist);
-	unsigned* toff = (unsigned*) ((char*) ws + L.toff);
-	unsigned* partial = (unsigned*) ((char*) ws + L.partial);
-	unsigned* tinfo = (unsigned*) ((char*) ws + L.tinfo);
+	const clo_radix_counters c = rp_counters(ws, L, 0);   // (the tiles of a launch are in its tables)
 	const auto up = [](size_t x) { return (x + 255) & ~(size_t) 255; };
 	// the segments as they lie after the first pass: back to back, in order
 	size_t seg_base[CLO_SEG_MAX];
@@ -658,43 +692,25 @@ int rp_sort_seg_impl(const E* src, const E* src2, E* a, E* b, size_t n, const si
 	const E* cur_in = src;
 	for (int p = 0; p < passes; ++p) {
 		const clo_seg_tables& sgp = p == 0 ? sg0 : sg;
-		const unsigned grid = (sgp.ntiles + 7u) / 8u * 8u;
 		E* cur_out = p % 2 == 0 ? b : a;
-		const int rem = key_bits - p * PB;
-		const int bits = rem < PB ? rem : PB;
-		const int lo_bits = bits < LB ? bits : LB, hi_bits = bits - lo_bits;
-		const unsigned shift = (unsigned) (key_shift + p * PB);
-		const unsigned mask_lo = (1u << lo_bits) - 1u, mask_hi = (1u << hi_bits) - 1u;
+		const rp_digits d = rp_pass_digits<LB, HB>(p, key_shift, key_bits);
 		{
 			clo_timing_scope timing("radix_hist", s);
 			const int st = (dig && p > 0)
-				? clo_radixw_launch_tilehist_bytes_seg(dig, sgp, (int) sizeof(E), PB, (mask_hi << LB) | mask_lo, thist, tinfo, partial, L.big, s)
-				: clo_radixw_launch_tilehist_seg(cur_in, p == 0 ? src2 : nullptr, sgp, (int) sizeof(E), PB, shift, (mask_hi << LB) | mask_lo, thist, tinfo, partial, L.big, s);
+				? clo_radixw_launch_tilehist_bytes_seg(dig, sgp, (int) sizeof(E), PB, d.mask, c, s)
+				: clo_radixw_launch_tilehist_seg(cur_in, p == 0 ? src2 : nullptr, sgp, (int) sizeof(E), PB, d.shift, d.mask, c, s);
 			if (st != 0) return st;
 		}
 		const unsigned* dbase = nullptr;
 		{
 			clo_timing_scope timing("radix_offsets", s);
-			const int st = clo_radixw_launch_offsets_seg(PB, thist, sgp, partial, toff, &dbase, s);
+			const int st = clo_radixw_launch_offsets_seg(PB, c, sgp, &dbase, s);
 			if (st != 0) return st;
 		}
 		{
 			clo_timing_scope timing("radix_pass", s);
-			const unsigned next_shift = (unsigned) (key_shift + (p + 1) * PB);
-			if (L.big) {
-				if (dig && p + 1 < passes)
-					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, true, true>), dim3(grid), dim3(pair_shape<E, true>::THREADS), 0, s,
-						(const E*) cur_in, cur_out, (size_t) sgp.ntiles, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, 0,
-						kx_none, kx_none, dig, next_shift, sgp.tiles, p == 0 ? src2 : (const E*) nullptr);
-				else
-					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, false, true>), dim3(grid), dim3(pair_shape<E, true>::THREADS), 0, s,
-						(const E*) cur_in, cur_out, (size_t) sgp.ntiles, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, 0,
-						kx_none, kx_none, nullptr, 0u, sgp.tiles, p == 0 ? src2 : (const E*) nullptr);
-			} else {
-				hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, false, false, true>), dim3(grid), dim3(pair_shape<E, false>::THREADS), 0, s,
-					(const E*) cur_in, cur_out, (size_t) sgp.ntiles, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, 0,
-					kx_none, kx_none, nullptr, 0u, sgp.tiles, p == 0 ? src2 : (const E*) nullptr);
-			}
+			rp_launch_pass<E, LB, HB, true>(c, d, cur_in, cur_out, (size_t) sgp.ntiles, dbase, 0, kx_none, kx_none, p + 1 < passes ? dig : nullptr, s,
+				sgp.tiles, p == 0 ? src2 : nullptr);
 		}
 		cur_in = cur_out;
 	}
@@ -776,107 +792,6 @@ int kv_unpack(const uint64_t* pairs, const clo_kv_io& io, size_t n, int key_size
 	}
 	#undef CLO_KVU
 	return (int) hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Key-value sorts (clo_hip_radix_sort_kv), host side.
-//
-// The chain-free passes of radix 16 / 256 (LB = HB = 4): the first pass and its histogram read the two arrays, the
-// last pass writes them, the passes in between are the 8-byte pair passes as they are. Bytes per element for 32-bit
-// keys and values: histogram 4 (keys only), first pass 8 in + 8 out, middle passes 16 each (+ the digit stream), last
-// pass 8 + 8 — the AoS pair sort's traffic, less half of its first histogram.
-// ---------------------------------------------------------------------------
-template <int KB, bool BIG, bool DIG, int KVI, int KVO>
-void kv_launch_pass(const uint64_t* in, uint64_t* out, size_t n, unsigned tiles, unsigned shift, unsigned mask_lo, unsigned mask_hi,
-	const unsigned* thist, const unsigned* toff, const unsigned* dbase, const unsigned* tinfo, int aligned, clo_keyx kin, clo_keyx kout,
-	unsigned char* dig, unsigned next_shift, const clo_kv_io& io, hipStream_t s) {
-	hipLaunchKernelGGL((clo_radix4_pair_kernel<uint64_t, 4, 4, BIG, DIG, false, KVI, KVO>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<uint64_t, BIG>::THREADS), 0, s,
-		in, out, n, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned, kin, kout, dig, next_shift, (const clo_seg_tile*) nullptr, (const uint64_t*) nullptr, io);
-}
-
-template <int KB, bool BIG>
-void kv_launch(bool first, bool last, bool dig, const uint64_t* in, uint64_t* out, size_t n, unsigned tiles, unsigned shift, unsigned mask_lo, unsigned mask_hi,
-	const unsigned* thist, const unsigned* toff, const unsigned* dbase, const unsigned* tinfo, int aligned, clo_keyx kin, clo_keyx kout,
-	unsigned char* dig_out, unsigned next_shift, const clo_kv_io& io, hipStream_t s) {
-	#define CLO_KVL(D, I, O) kv_launch_pass<KB, BIG, D, I, O>(in, out, n, tiles, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned, kin, kout, dig_out, next_shift, io, s)
-	if (first && last) CLO_KVL(false, KB, KB);
-	else if (last) CLO_KVL(false, 0, KB);
-	else if (first && BIG && dig) CLO_KVL(BIG, KB, 0);   // (the digit stream goes with the big tiles)
-	else if (first) CLO_KVL(false, KB, 0);
-	#undef CLO_KVL
-}
-
-template <int KB>
-int rp_sort_kv_impl(const clo_kv_io& io, uint64_t* pa, uint64_t* pb, size_t n, int key_shift, int key_bits, clo_keyx kx, void* ws, hipStream_t s) {
-	constexpr int LB = 4, HB = 4, PB = 8;
-	typedef uint64_t E;
-	const int passes = (key_bits + PB - 1) / PB;
-	const rp_layout L = rp_make_layout(n, (int) sizeof(E), PB);
-	unsigned* thist = (unsigned*) ((char*) ws + L.thist);
-	unsigned* toff = (unsigned*) ((char*) ws + L.toff);
-	unsigned* partial = (unsigned*) ((char*) ws + L.partial);
-	unsigned* tinfo = (unsigned*) ((char*) ws + L.tinfo);
-	const unsigned tiles = (unsigned) L.tiles;
-	const bool big = clo_radix_big_tiles(n, (int) sizeof(E));
-	unsigned char* dig = (L.dig != 0 && passes > 1 && !clo_hip_env()->no_digits) ? (unsigned char*) ws + L.dig : nullptr;
-	const clo_keyx kx_none = { 0, 0, 0 };
-	// One pass that reads and writes the caller's arrays cannot run in place (other tiles' results land on keys
-	// this tile has not read yet): it writes the pairs, and the unpack kernel splits them.
-	const bool split_after = passes == 1 && (io.keys_out == io.keys_in || (const void*) io.values_out == (const void*) io.values_in);
-	const bool vec_ok = (uintptr_t) io.keys_in % 16 == 0 && (uintptr_t) io.values_in % 16 == 0;
-	const E* cur_in = nullptr;
-	for (int p = 0; p < passes; ++p) {
-		const bool first = p == 0, last = p + 1 == passes && !split_after;   // last: this pass writes the caller's arrays
-		E* cur_out = last ? nullptr : (p % 2 == 0 ? pa : pb);
-		const int rem = key_bits - p * PB;
-		const int bits = rem < PB ? rem : PB;
-		const int lo_bits = bits < LB ? bits : LB, hi_bits = bits - lo_bits;
-		const unsigned shift = (unsigned) (key_shift + p * PB);
-		const unsigned mask_lo = (1u << lo_bits) - 1u, mask_hi = (1u << hi_bits) - 1u;
-		{
-			clo_timing_scope timing("radix_hist", s);
-			const int st = first
-				? clo_radixw_launch_tilehist_kv(io.keys_in, n, KB, PB, shift, (mask_hi << LB) | mask_lo, thist, tinfo, partial, tiles, big, kx, s)
-				: (dig ? clo_radixw_launch_tilehist_bytes(dig, n, (int) sizeof(E), PB, (mask_hi << LB) | mask_lo, thist, tinfo, partial, tiles, big, s)
-				       : clo_radixw_launch_tilehist(cur_in, n, (int) sizeof(E), PB, shift, (mask_hi << LB) | mask_lo, thist, tinfo, partial, tiles, big, kx_none, s));
-			if (st != 0) return st;
-		}
-		const unsigned* dbase = nullptr;
-		{
-			clo_timing_scope timing("radix_offsets", s);
-			const int st = clo_radixw_launch_offsets(PB, thist, tiles, partial, toff, &dbase, s);
-			if (st != 0) return st;
-		}
-		{
-			clo_timing_scope timing("radix_pass", s);
-			const int aligned = first ? (int) vec_ok : (int) ((uintptr_t) cur_in % 16 == 0);
-			const clo_keyx kin = first ? kx : kx_none, kout = p + 1 == passes ? kx : kx_none;
-			const unsigned next_shift = (unsigned) (key_shift + (p + 1) * PB);
-			if (!first && !last) {   // a middle pass: the pair passes as they are
-				if (big && dig)
-					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, true>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, true>::THREADS), 0, s,
-						cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout,
-						dig, next_shift);
-				else if (big)
-					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, true, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, true>::THREADS), 0, s,
-						cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout, nullptr, 0u);
-				else
-					hipLaunchKernelGGL((clo_radix4_pair_kernel<E, LB, HB, false, false>), dim3((tiles + 7u) / 8u * 8u), dim3(pair_shape<E, false>::THREADS), 0, s,
-						cur_in, cur_out, n, shift, mask_lo, mask_hi, (const unsigned*) thist, (const unsigned*) toff, dbase, (const unsigned*) tinfo, aligned, kin, kout, nullptr, 0u);
-			} else if (big) {
-				kv_launch<KB, true>(first, last, dig != nullptr && p + 1 < passes, cur_in, cur_out, n, tiles, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned,
-					kin, kout, dig, next_shift, io, s);
-			} else {
-				kv_launch<KB, false>(first, last, false, cur_in, cur_out, n, tiles, shift, mask_lo, mask_hi, thist, toff, dbase, tinfo, aligned,
-					kin, kout, nullptr, 0u, io, s);
-			}
-		}
-		cur_in = cur_out;
-	}
-	hipError_t e = hipGetLastError();
-	if (e != hipSuccess) return (int) e;
-	if (split_after) return kv_unpack(pa, io, n, KB, s);
-	return 0;
 }
 
 }  // namespace
@@ -987,9 +902,9 @@ int clo_radix4_sort_kv(const clo_kv_io& io, void* pairs_a, void* pairs_b, size_t
 	const bool small = n <= (size_t) small_big<uint64_t>::TILE && digit_bits <= 4;   // (clo_radix4_sort's one-launch case)
 	if ((digit_bits == 4 || digit_bits == 8) && !small && !clo_radix1_applies(n, 8, digit_bits)) {
 		switch (key_size) {
-			case 1: return rp_sort_kv_impl<1>(io, pa, pb, n, key_shift, key_bits, kx, ws, s);
-			case 2: return rp_sort_kv_impl<2>(io, pa, pb, n, key_shift, key_bits, kx, ws, s);
-			case 4: return rp_sort_kv_impl<4>(io, pa, pb, n, key_shift, key_bits, kx, ws, s);
+			case 1: return rp_sort_impl<uint64_t, 4, 4, 1>(nullptr, pa, pb, n, key_shift, key_bits, kx, nullptr, io, ws, s);
+			case 2: return rp_sort_impl<uint64_t, 4, 4, 2>(nullptr, pa, pb, n, key_shift, key_bits, kx, nullptr, io, ws, s);
+			case 4: return rp_sort_impl<uint64_t, 4, 4, 4>(nullptr, pa, pb, n, key_shift, key_bits, kx, nullptr, io, ws, s);
 			default: return CLO_HIP_EUNSUPPORTED;
 		}
 	}

@@ -546,45 +546,44 @@ int clo_radixw_seg_build(const size_t* piece_n, const size_t* piece_base, const 
 size_t clo_radixw_partial_rows_seg(size_t chunks, size_t nseg) { return chunks + 1 + nseg; }
 
 template <typename E>
-static int rw_launch_tilehist_seg(const void* in, const void* in2, const clo_seg_tables& sg, int bits, unsigned shift, unsigned mask, unsigned* thist,
-	unsigned* tinfo, unsigned* partial, bool big, hipStream_t s) {
+static int rw_launch_tilehist_seg(const void* in, const void* in2, const clo_seg_tables& sg, int bits, unsigned shift, unsigned mask,
+	const clo_radix_counters& c, hipStream_t s) {
 	const unsigned clear_words = (sg.nchunks + 1u) << bits;
 	const clo_keyx kx_none = { 0, 0, 0 };
 	if (bits != 8) return CLO_HIP_EUNSUPPORTED;   // (the segmented sorts run the radix-16 / 256 schedule only)
-	if (big) hipLaunchKernelGGL((clo_radixw_tilehist_kernel<E, 8, true, true>), dim3(sg.ntiles), dim3(rw_shape<E, true>::THREADS), 0, s,
-		(const E*) in, (size_t) 0, shift, mask, thist, tinfo, 0, kx_none, partial, clear_words, sg.tiles, (const E*) in2);
+	if (c.big) hipLaunchKernelGGL((clo_radixw_tilehist_kernel<E, 8, true, true>), dim3(sg.ntiles), dim3(rw_shape<E, true>::THREADS), 0, s,
+		(const E*) in, (size_t) 0, shift, mask, c.thist, c.tinfo, 0, kx_none, c.partial, clear_words, sg.tiles, (const E*) in2);
 	else hipLaunchKernelGGL((clo_radixw_tilehist_kernel<E, 8, false, true>), dim3(sg.ntiles), dim3(rw_shape<E, false>::THREADS), 0, s,
-		(const E*) in, (size_t) 0, shift, mask, thist, tinfo, 0, kx_none, partial, clear_words, sg.tiles, (const E*) in2);
+		(const E*) in, (size_t) 0, shift, mask, c.thist, c.tinfo, 0, kx_none, c.partial, clear_words, sg.tiles, (const E*) in2);
 	return (int) hipGetLastError();
 }
 
 int clo_radixw_launch_tilehist_seg(const void* in, const void* in2, const clo_seg_tables& sg, int elem_size, int bits, unsigned shift, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, bool big, hipStream_t s) {
+	const clo_radix_counters& c, hipStream_t s) {
 	switch (elem_size) {
-		case 4: return rw_launch_tilehist_seg<uint32_t>(in, in2, sg, bits, shift, mask, thist, tinfo, partial, big, s);
-		case 8: return rw_launch_tilehist_seg<uint64_t>(in, in2, sg, bits, shift, mask, thist, tinfo, partial, big, s);
+		case 4: return rw_launch_tilehist_seg<uint32_t>(in, in2, sg, bits, shift, mask, c, s);
+		case 8: return rw_launch_tilehist_seg<uint64_t>(in, in2, sg, bits, shift, mask, c, s);
 		default: return CLO_HIP_EUNSUPPORTED;
 	}
 }
 
 int clo_radixw_launch_tilehist_bytes_seg(const unsigned char* dig, const clo_seg_tables& sg, int elem_size, int bits, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, bool big, hipStream_t s) {
+	const clo_radix_counters& c, hipStream_t s) {
 	const unsigned clear_words = (sg.nchunks + 1u) << bits;
-	if (bits != 8 || !big) return CLO_HIP_EUNSUPPORTED;
+	if (bits != 8 || !c.big) return CLO_HIP_EUNSUPPORTED;
 	if (elem_size == 8) hipLaunchKernelGGL((clo_radixw_tilehist_bytes_kernel<8, 16, 1024, true, 2>), dim3((sg.ntiles + 1u) / 2u), dim3(1024), 0, s,
-		dig, (size_t) 0, sg.ntiles, mask, thist, tinfo, partial, clear_words, sg.tiles);
+		dig, (size_t) 0, sg.ntiles, mask, c.thist, c.tinfo, c.partial, clear_words, sg.tiles);
 	else if (elem_size == 4) hipLaunchKernelGGL((clo_radixw_tilehist_bytes_kernel<8, 32, 1024, true, 2>), dim3((sg.ntiles + 1u) / 2u), dim3(1024), 0, s,
-		dig, (size_t) 0, sg.ntiles, mask, thist, tinfo, partial, clear_words, sg.tiles);
+		dig, (size_t) 0, sg.ntiles, mask, c.thist, c.tinfo, c.partial, clear_words, sg.tiles);
 	else return CLO_HIP_EUNSUPPORTED;
 	return (int) hipGetLastError();
 }
 
-int clo_radixw_launch_offsets_seg(int bits, const unsigned* thist, const clo_seg_tables& sg, unsigned* partial, unsigned* toff,
-	const unsigned** dbase, hipStream_t s) {
+int clo_radixw_launch_offsets_seg(int bits, const clo_radix_counters& c, const clo_seg_tables& sg, const unsigned** dbase, hipStream_t s) {
 	if (bits != 8) return CLO_HIP_EUNSUPPORTED;
 	hipLaunchKernelGGL((clo_radixw_offsets_lb_kernel<256, true>), dim3(sg.nchunks), dim3(RW_CS_THREADS), 0, s,
-		thist, sg.ntiles, sg.nchunks, partial, toff, sg.chunks);
-	*dbase = partial + ((size_t) (sg.nchunks + 1u) << bits);
+		c.thist, sg.ntiles, sg.nchunks, c.partial, c.toff, sg.chunks);
+	*dbase = c.partial + ((size_t) (sg.nchunks + 1u) << bits);
 	return (int) hipGetLastError();
 }
 
@@ -594,15 +593,15 @@ int clo_radixw_launch_offsets_seg(int bits, const unsigned* thist, const clo_seg
 unsigned clo_radixw_clear_words(int bits, unsigned tiles);
 
 template <typename E>
-static int rw_launch_tilehist(const void* in, size_t n, int bits, unsigned shift, unsigned mask, unsigned* thist, unsigned* tinfo,
-	unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s) {
+static int rw_launch_tilehist(const void* in, size_t n, int bits, unsigned shift, unsigned mask, const clo_radix_counters& c, clo_keyx kx,
+	hipStream_t s) {
 	const int aligned = (int) ((uintptr_t) in % 16 == 0);
-	const unsigned clear_words = partial ? clo_radixw_clear_words(bits, tiles) : 0u;
+	const unsigned clear_words = c.partial ? clo_radixw_clear_words(bits, c.tiles) : 0u;
 	#define CLO_RW_TH(B) case B: \
-		if (big && sizeof(E) >= 4) hipLaunchKernelGGL((clo_radixw_tilehist_kernel<E, B, (sizeof(E) >= 4)>), dim3(tiles), dim3(rw_shape<E, (sizeof(E) >= 4)>::THREADS), 0, s, \
-			(const E*) in, n, shift, mask, thist, tinfo, aligned, kx, partial, clear_words); \
-		else hipLaunchKernelGGL((clo_radixw_tilehist_kernel<E, B, false>), dim3(tiles), dim3(rw_shape<E, false>::THREADS), 0, s, \
-			(const E*) in, n, shift, mask, thist, tinfo, aligned, kx, partial, clear_words); \
+		if (c.big && sizeof(E) >= 4) hipLaunchKernelGGL((clo_radixw_tilehist_kernel<E, B, (sizeof(E) >= 4)>), dim3(c.tiles), dim3(rw_shape<E, (sizeof(E) >= 4)>::THREADS), 0, s, \
+			(const E*) in, n, shift, mask, c.thist, c.tinfo, aligned, kx, c.partial, clear_words); \
+		else hipLaunchKernelGGL((clo_radixw_tilehist_kernel<E, B, false>), dim3(c.tiles), dim3(rw_shape<E, false>::THREADS), 0, s, \
+			(const E*) in, n, shift, mask, c.thist, c.tinfo, aligned, kx, c.partial, clear_words); \
 		break
 	switch (bits) {
 		CLO_RW_TH(1); CLO_RW_TH(2); CLO_RW_TH(3); CLO_RW_TH(4); CLO_RW_TH(5); CLO_RW_TH(6); CLO_RW_TH(7); CLO_RW_TH(8);
@@ -615,51 +614,50 @@ static int rw_launch_tilehist(const void* in, size_t n, int bits, unsigned shift
 // `big`: the tiles are those of clo_radix_big_tiles(n, elem_size) (clo_hip_radix_rank.h); `partial`: the
 // counter scan's workspace (clo_radixw_launch_offsets follows on the same stream), whose hand-off words this launch zeroes
 int clo_radixw_launch_tilehist(const void* in, size_t n, int elem_size, int bits, unsigned shift, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s) {
+	const clo_radix_counters& c, clo_keyx kx, hipStream_t s) {
 	switch (elem_size) {
-		case 1: return rw_launch_tilehist<uint8_t>(in, n, bits, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
-		case 2: return rw_launch_tilehist<uint16_t>(in, n, bits, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
-		case 4: return rw_launch_tilehist<uint32_t>(in, n, bits, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
-		case 8: return rw_launch_tilehist<uint64_t>(in, n, bits, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
+		case 1: return rw_launch_tilehist<uint8_t>(in, n, bits, shift, mask, c, kx, s);
+		case 2: return rw_launch_tilehist<uint16_t>(in, n, bits, shift, mask, c, kx, s);
+		case 4: return rw_launch_tilehist<uint32_t>(in, n, bits, shift, mask, c, kx, s);
+		case 8: return rw_launch_tilehist<uint64_t>(in, n, bits, shift, mask, c, kx, s);
 		default: return CLO_HIP_EUNSUPPORTED;
 	}
 }
 
 // The first histogram of a key-value sort: pair tiles, keys alone (one digit width: the radix-16 / 256 schedule's 8 bits).
 template <typename K>
-static int rw_launch_tilehist_kv(const void* keys, size_t n, unsigned shift, unsigned mask, unsigned* thist, unsigned* tinfo,
-	unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s) {
+static int rw_launch_tilehist_kv(const void* keys, size_t n, unsigned shift, unsigned mask, const clo_radix_counters& c, clo_keyx kx, hipStream_t s) {
 	const int aligned = (int) ((uintptr_t) keys % 16 == 0);
-	const unsigned clear_words = partial ? clo_radixw_clear_words(8, tiles) : 0u;
-	if (big)
-		hipLaunchKernelGGL((clo_radixw_tilehist_kernel<uint64_t, 8, true, false, 1, K>), dim3(tiles), dim3(rw_shape<uint64_t, true>::THREADS), 0, s,
-			(const K*) keys, n, shift, mask, thist, tinfo, aligned, kx, partial, clear_words, nullptr, nullptr);
+	const unsigned clear_words = c.partial ? clo_radixw_clear_words(8, c.tiles) : 0u;
+	if (c.big)
+		hipLaunchKernelGGL((clo_radixw_tilehist_kernel<uint64_t, 8, true, false, 1, K>), dim3(c.tiles), dim3(rw_shape<uint64_t, true>::THREADS), 0, s,
+			(const K*) keys, n, shift, mask, c.thist, c.tinfo, aligned, kx, c.partial, clear_words, nullptr, nullptr);
 	else
-		hipLaunchKernelGGL((clo_radixw_tilehist_kernel<uint64_t, 8, false, false, 1, K>), dim3(tiles), dim3(rw_shape<uint64_t, false>::THREADS), 0, s,
-			(const K*) keys, n, shift, mask, thist, tinfo, aligned, kx, partial, clear_words, nullptr, nullptr);
+		hipLaunchKernelGGL((clo_radixw_tilehist_kernel<uint64_t, 8, false, false, 1, K>), dim3(c.tiles), dim3(rw_shape<uint64_t, false>::THREADS), 0, s,
+			(const K*) keys, n, shift, mask, c.thist, c.tinfo, aligned, kx, c.partial, clear_words, nullptr, nullptr);
 	return (int) hipGetLastError();
 }
 
 int clo_radixw_launch_tilehist_kv(const void* keys, size_t n, int key_size, int bits, unsigned shift, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, clo_keyx kx, hipStream_t s) {
+	const clo_radix_counters& c, clo_keyx kx, hipStream_t s) {
 	if (bits != 8) return CLO_HIP_EUNSUPPORTED;
 	switch (key_size) {
-		case 1: return rw_launch_tilehist_kv<uint8_t>(keys, n, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
-		case 2: return rw_launch_tilehist_kv<uint16_t>(keys, n, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
-		case 4: return rw_launch_tilehist_kv<uint32_t>(keys, n, shift, mask, thist, tinfo, partial, tiles, big, kx, s);
+		case 1: return rw_launch_tilehist_kv<uint8_t>(keys, n, shift, mask, c, kx, s);
+		case 2: return rw_launch_tilehist_kv<uint16_t>(keys, n, shift, mask, c, kx, s);
+		case 4: return rw_launch_tilehist_kv<uint32_t>(keys, n, shift, mask, c, kx, s);
 		default: return CLO_HIP_EUNSUPPORTED;
 	}
 }
 
 // Histograms out of the digit stream (tiles of the shape `big` names).
 int clo_radixw_launch_tilehist_bytes(const unsigned char* dig, size_t n, int elem_size, int bits, unsigned mask,
-	unsigned* thist, unsigned* tinfo, unsigned* partial, unsigned tiles, bool big, hipStream_t s) {
-	const unsigned clear_words = partial ? clo_radixw_clear_words(bits, tiles) : 0u;
-	#define CLO_RW_THB1(B, I, T, W) hipLaunchKernelGGL((clo_radixw_tilehist_bytes_kernel<B, I, T, false, W>), dim3((tiles + W - 1u) / W), dim3(T), 0, s, dig, n, tiles, mask, thist, tinfo, partial, clear_words)
+	const clo_radix_counters& c, hipStream_t s) {
+	const unsigned clear_words = c.partial ? clo_radixw_clear_words(bits, c.tiles) : 0u;
+	#define CLO_RW_THB1(B, I, T, W) hipLaunchKernelGGL((clo_radixw_tilehist_bytes_kernel<B, I, T, false, W>), dim3((c.tiles + W - 1u) / W), dim3(T), 0, s, dig, n, c.tiles, mask, c.thist, c.tinfo, c.partial, clear_words)
 	/* 4-byte elements (round 5): two 16 384-byte tiles per work-group as well, 32 bytes per thread in flight (histograms -3 %, 2^26 / 2^27 sorts -0.8 %) */
 	#define CLO_RW_THB4(B) CLO_RW_THB1(B, 32, 1024, 2u)
 	#define CLO_RW_THB(B) case B: \
-		if (!big) return CLO_HIP_EUNSUPPORTED;   /* (the stream goes with the big tiles) */ \
+		if (!c.big) return CLO_HIP_EUNSUPPORTED;   /* (the stream goes with the big tiles) */ \
 		if (elem_size == 8) CLO_RW_THB1(B, 16, 1024, 2u); else CLO_RW_THB4(B); \
 		break
 	if (elem_size != 4 && elem_size != 8) return CLO_HIP_EUNSUPPORTED;
@@ -682,13 +680,12 @@ unsigned clo_radixw_clear_words(int bits, unsigned tiles) {
 size_t clo_radixw_partial_rows(size_t tiles) { const size_t chunk = (size_t) rw_chunk_for((unsigned) (tiles > 0xffffffffull ? 0xffffffffull : tiles)); return (tiles + chunk - 1) / chunk + 2; }
 
 // *dbase: null — toff holds the final offsets (one tile) —, or the row of digit bases the consumer adds to toff[tile][digit].
-int clo_radixw_launch_offsets(int bits, const unsigned* thist, unsigned tiles, unsigned* partial, unsigned* toff,
-	const unsigned** dbase, hipStream_t s) {
-	const unsigned chunk = (unsigned) rw_chunk_for(tiles);
-	const unsigned chunks = (tiles + chunk - 1) / chunk;
+int clo_radixw_launch_offsets(int bits, const clo_radix_counters& c, const unsigned** dbase, hipStream_t s) {
+	const unsigned chunk = (unsigned) rw_chunk_for(c.tiles);
+	const unsigned chunks = (c.tiles + chunk - 1) / chunk;
 	*dbase = nullptr;
-	#define CLO_RW_OFF1(B) case B: hipLaunchKernelGGL((clo_radixw_offsets1_kernel<(1 << B)>), dim3(1), dim3(256), 0, s, thist, tiles, toff); break
-	if (tiles == 1) {
+	#define CLO_RW_OFF1(B) case B: hipLaunchKernelGGL((clo_radixw_offsets1_kernel<(1 << B)>), dim3(1), dim3(256), 0, s, c.thist, c.tiles, c.toff); break
+	if (c.tiles == 1) {
 		switch (bits) {
 			CLO_RW_OFF1(1); CLO_RW_OFF1(2); CLO_RW_OFF1(3); CLO_RW_OFF1(4); CLO_RW_OFF1(5); CLO_RW_OFF1(6); CLO_RW_OFF1(7); CLO_RW_OFF1(8);
 			default: return CLO_HIP_EUNSUPPORTED;
@@ -697,15 +694,15 @@ int clo_radixw_launch_offsets(int bits, const unsigned* thist, unsigned tiles, u
 	}
 	#undef CLO_RW_OFF1
 	#define CLO_RW_LB(B) case B: \
-		if (chunk == (unsigned) RW_CHUNK) hipLaunchKernelGGL((clo_radixw_offsets_lb_kernel<(1 << B), false, RW_CHUNK>), dim3(chunks), dim3(RW_CS_THREADS), 0, s, thist, tiles, chunks, partial, toff); \
-		else hipLaunchKernelGGL((clo_radixw_offsets_lb_kernel<(1 << B), false, RW_CHUNK_SMALL>), dim3(chunks), dim3(RW_CS_THREADS), 0, s, thist, tiles, chunks, partial, toff); \
+		if (chunk == (unsigned) RW_CHUNK) hipLaunchKernelGGL((clo_radixw_offsets_lb_kernel<(1 << B), false, RW_CHUNK>), dim3(chunks), dim3(RW_CS_THREADS), 0, s, c.thist, c.tiles, chunks, c.partial, c.toff); \
+		else hipLaunchKernelGGL((clo_radixw_offsets_lb_kernel<(1 << B), false, RW_CHUNK_SMALL>), dim3(chunks), dim3(RW_CS_THREADS), 0, s, c.thist, c.tiles, chunks, c.partial, c.toff); \
 		break
 	switch (bits) {
 		CLO_RW_LB(1); CLO_RW_LB(2); CLO_RW_LB(3); CLO_RW_LB(4); CLO_RW_LB(5); CLO_RW_LB(6); CLO_RW_LB(7); CLO_RW_LB(8);
 		default: return CLO_HIP_EUNSUPPORTED;
 	}
 	#undef CLO_RW_LB
-	*dbase = partial + ((size_t) (chunks + 1u) << bits);
+	*dbase = c.partial + ((size_t) (chunks + 1u) << bits);
 	return (int) hipGetLastError();
 }
 
