@@ -215,7 +215,7 @@ size_t clo_hip_scan_typed_workspace_bytes(size_t numel, int sum_type) {
 int clo_hip_scan_exclusive_typed(const void* data_in, void* data_out, size_t numel, int elem_type, int sum_type,
 	void* workspace, size_t workspace_bytes, void* stream) {
 	if (numel == 0) return 0;
-	if (!data_in || !data_out || !workspace) return CLO_HIP_EARGS;
+	if (!data_in || !data_out || !workspace || clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	if (!clo_hip_scan_is_typed(elem_type, sum_type)) return CLO_HIP_EUNSUPPORTED;
 	if (workspace_bytes < clo_hip_scan_typed_workspace_bytes(numel, sum_type)) return CLO_HIP_EWORKSPACE;
 	hipStream_t s = (hipStream_t) stream;
@@ -244,7 +244,7 @@ size_t clo_hip_scan_fp_workspace_bytes(size_t numel, int sum_size) {
 int clo_hip_scan_exclusive_fp(const void* data_in, void* data_out, size_t numel, int elem_type, int sum_size,
 	void* workspace, size_t workspace_bytes, void* stream) {
 	if (numel == 0) return 0;
-	if (!data_in || !data_out || !workspace) return CLO_HIP_EARGS;
+	if (!data_in || !data_out || !workspace || clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	if (sum_size != 4 && sum_size != 8) return CLO_HIP_EUNSUPPORTED;
 	if (workspace_bytes < clo_hip_scan_fp_workspace_bytes(numel, sum_size)) return CLO_HIP_EWORKSPACE;
 	hipStream_t s = (hipStream_t) stream;

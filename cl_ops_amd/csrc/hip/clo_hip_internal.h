@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "clo_hip.h"
+
 // ---- workspace header (first CLO_WS_HEADER_BYTES of every workspace) ----
 // word 0: status (non-zero = a bounded spin gave up)
 // word 2: epoch of the last completed call (scan), word 3: work-groups that have left
@@ -27,6 +29,11 @@
 struct clo_hip_env_t { unsigned max_spins; int radix_sweep; int r1_pools; int no_digits; int bitonic_merge2; };
 const clo_hip_env_t* clo_hip_env();
 int clo_radixw_preload();   // clo_hip_radixw.hip
+
+// A scratch or atomic-target pointer of the C-ABI that breaks its alignment rule (include/clo_hip.h: a workspace
+// CLO_HIP_WORKSPACE_ALIGN bytes, a device uint64 word 8); NULL is not misaligned (each entry says where it is allowed).
+inline bool clo_misaligned(const void* p, size_t align) { return ((uintptr_t) p & (align - 1)) != 0; }
+inline bool clo_ws_misaligned(const void* ws) { return clo_misaligned(ws, CLO_HIP_WORKSPACE_ALIGN); }
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>

@@ -90,7 +90,7 @@ int clo_hip_radix_sort_fed(const void* src, void* dst, void* tmp, size_t numel,
 	void* workspace, size_t workspace_bytes, void* stream) {
 
 	if (numel == 0) return 0;
-	if (!src || !dst || !tmp || !workspace || tmp == src || tmp == dst) return CLO_HIP_EARGS;
+	if (!src || !dst || !tmp || !workspace || tmp == src || tmp == dst || clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	if (key_bits < 1 || key_shift < 0 || key_shift + key_bits > 8 * elem_size) return CLO_HIP_EARGS;
 	if (key_kind < 0 || key_kind > 2) return CLO_HIP_EARGS;
 	if (key_kind == 2 && key_bits != 16 && key_bits != 32 && key_bits != 64) return CLO_HIP_EARGS;
@@ -111,7 +111,7 @@ int clo_hip_radix_sort_kv(const void* keys_in, const void* values_in, void* keys
 	size_t numel, int key_size, int key_shift, int key_bits, int key_kind, int digit_bits,
 	void* workspace, size_t workspace_bytes, void* stream) {
 	if (numel == 0) return 0;
-	if (!keys_in || !values_out || !pairs_a || !pairs_b || pairs_a == pairs_b || !workspace) return CLO_HIP_EARGS;
+	if (!keys_in || !values_out || !pairs_a || !pairs_b || pairs_a == pairs_b || !workspace || clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	const void* arrays[4] = { keys_in, values_in, keys_out, values_out };
 	for (int i = 0; i < 4; ++i) if (arrays[i] == pairs_a || arrays[i] == pairs_b) return CLO_HIP_EARGS;
 	if (key_size != 1 && key_size != 2 && key_size != 4) return CLO_HIP_EUNSUPPORTED;
@@ -147,6 +147,7 @@ int clo_hip_radix_sort_segmented2(const void* src, const void* src2, void* a, vo
 	*result_in_b = 0;
 	if (numel == 0) return 0;
 	if (!src || !a || !b || a == b || src == b || !workspace || !seg_counts || nseg < 1 || nseg > CLO_SEG_MAX) return CLO_HIP_EARGS;
+	if (clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	if (npieces < 0 || npieces > CLO_SEG_MAX || (npieces > 0 && (!piece_counts || !piece_offsets || !piece_segment))) return CLO_HIP_EARGS;
 	if (elem_size != 4 && elem_size != 8) return CLO_HIP_EUNSUPPORTED;
 	if (digit_bits != 4 && digit_bits != 8) return CLO_HIP_EUNSUPPORTED;
@@ -179,7 +180,7 @@ size_t clo_hip_msd_workspace_bytes(size_t numel, int elem_size, int bucket_bits)
 
 int clo_hip_msd_histogram(const void* src, size_t numel, int elem_size,
 	int key_shift, int key_bits, int bucket_bits, uint64_t* counts_dev, void* stream) {
-	if (!counts_dev || bucket_bits < 1 || bucket_bits > 3 || bucket_bits > key_bits) return CLO_HIP_EARGS;
+	if (!counts_dev || clo_misaligned(counts_dev, 8) || bucket_bits < 1 || bucket_bits > 3 || bucket_bits > key_bits) return CLO_HIP_EARGS;
 	hipStream_t s = (hipStream_t) stream;
 	hipError_t e = hipMemsetAsync(counts_dev, 0, sizeof(uint64_t) << bucket_bits, s);
 	if (e != hipSuccess) return (int) e;
@@ -198,6 +199,7 @@ int clo_hip_msd_partition(const void* src, void* dst, size_t numel, int elem_siz
 	void* workspace, size_t workspace_bytes, void* stream) {
 	hipStream_t s = (hipStream_t) stream;
 	if (bucket_bits < 1 || bucket_bits > 8 || bucket_bits > key_bits) return CLO_HIP_EARGS;
+	if (clo_misaligned(counts_dev, 8) || clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	if (numel == 0) {
 		if (counts_dev) return (int) hipMemsetAsync(counts_dev, 0, sizeof(uint64_t) << bucket_bits, s);
 		return 0;

@@ -181,7 +181,7 @@ int clo_hip_radix_jit_sort(void* handle, const void* src, void* dst, void* pairs
 	int digit_bits, void* workspace, size_t workspace_bytes, void* stream) {
 	radix_jit* rj = (radix_jit*) handle;
 	if (numel == 0) return 0;
-	if (!rj || !src || !dst || !pairs || !pairs_tmp || pairs == pairs_tmp) return CLO_HIP_EARGS;
+	if (!rj || !src || !dst || !pairs || !pairs_tmp || pairs == pairs_tmp || clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	if (numel > 0xffffffffull) return CLO_HIP_EARGS;
 	hipStream_t s = (hipStream_t) stream;
 	unsigned long n = numel;

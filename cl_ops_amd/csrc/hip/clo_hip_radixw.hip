@@ -173,7 +173,9 @@ void clo_radixw_tilehist_kernel(const L* __restrict__ in, size_t n, unsigned shi
 // 8-byte elements is 8 192 digit bytes — one 8-byte load per thread of a 1024-thread group left half as many
 // bytes in flight per CU as the 4-byte elements' 16 (150 us per launch against 98 for the same 256 MiB,
 // profiles/r04_satradix_u64_kernel_stats.csv); two such tiles share a group, 16 bytes per thread.
-template <int BITS, int ITEMS, int THREADS, bool SEG = false, int TPW = 1>   // ITEMS bytes per thread; THREADS / TPW * ITEMS = the tile
+// UA: the bytes start anywhere (a caller's first digits, clo_hip_radix_sort_fed); the library's own stream starts
+// 256-byte aligned.
+template <int BITS, int ITEMS, int THREADS, bool SEG = false, int TPW = 1, bool UA = false>   // ITEMS bytes per thread; THREADS / TPW * ITEMS = the tile
 __global__ __launch_bounds__(THREADS)
 void clo_radixw_tilehist_bytes_kernel(const unsigned char* __restrict__ dig, size_t n, unsigned tiles, unsigned mask, unsigned* __restrict__ thist,
 	unsigned* __restrict__ tinfo, unsigned* __restrict__ clear, unsigned clear_words, const clo_seg_tile* __restrict__ tdesc = nullptr) {
@@ -200,13 +202,13 @@ void clo_radixw_tilehist_bytes_kernel(const unsigned char* __restrict__ dig, siz
 	unsigned* const cnt = s_cnt + part * (R * COPIES) + (lane & (COPIES - 1));
 	typedef unsigned vecA __attribute__((ext_vector_type(ITEMS / 4)));   // (the stream starts 256-byte aligned, a tile is a multiple of 16 bytes)
 	typedef unsigned vecU __attribute__((ext_vector_type(ITEMS / 4), aligned(1)));   // (a segment starts at any byte of it)
-	typedef typename std::conditional<SEG, vecU, vecA>::type vecw;
+	typedef typename std::conditional<SEG || UA, vecU, vecA>::type vecw;
 	vecw v;
 	// (requested before the counters are zeroed: see clo_radixw_tilehist_kernel; lanes read adjacent 16-byte vectors)
 	if (count == (unsigned) TILE) {
 		typedef unsigned q4A __attribute__((ext_vector_type(4)));
 		typedef unsigned q4U __attribute__((ext_vector_type(4), aligned(1)));
-		typedef typename std::conditional<SEG, q4U, q4A>::type q4;
+		typedef typename std::conditional<SEG || UA, q4U, q4A>::type q4;
 		static_assert(ITEMS % 16 == 0, "whole 16-byte vectors per thread");
 		const q4* p = reinterpret_cast<const q4*>(dig + base) + ptid;
 		#pragma unroll
@@ -653,14 +655,19 @@ int clo_radixw_launch_tilehist_kv(const void* keys, size_t n, int key_size, int 
 int clo_radixw_launch_tilehist_bytes(const unsigned char* dig, size_t n, int elem_size, int bits, unsigned mask,
 	const clo_radix_counters& c, hipStream_t s) {
 	const unsigned clear_words = c.partial ? clo_radixw_clear_words(bits, c.tiles) : 0u;
-	#define CLO_RW_THB1(B, I, T, W) hipLaunchKernelGGL((clo_radixw_tilehist_bytes_kernel<B, I, T, false, W>), dim3((c.tiles + W - 1u) / W), dim3(T), 0, s, dig, n, c.tiles, mask, c.thist, c.tinfo, c.partial, clear_words)
+	#define CLO_RW_THB1(B, I, T, W, UA) hipLaunchKernelGGL((clo_radixw_tilehist_bytes_kernel<B, I, T, false, W, UA>), dim3((c.tiles + W - 1u) / W), dim3(T), 0, s, dig, n, c.tiles, mask, c.thist, c.tinfo, c.partial, clear_words)
 	/* 4-byte elements (round 5): two 16 384-byte tiles per work-group as well, 32 bytes per thread in flight (histograms -3 %, 2^26 / 2^27 sorts -0.8 %) */
-	#define CLO_RW_THB4(B) CLO_RW_THB1(B, 32, 1024, 2u)
+	#define CLO_RW_THB4(B) CLO_RW_THB1(B, 32, 1024, 2u, false)
 	#define CLO_RW_THB(B) case B: \
 		if (!c.big) return CLO_HIP_EUNSUPPORTED;   /* (the stream goes with the big tiles) */ \
-		if (elem_size == 8) CLO_RW_THB1(B, 16, 1024, 2u); else CLO_RW_THB4(B); \
+		if (elem_size == 8) CLO_RW_THB1(B, 16, 1024, 2u, false); else CLO_RW_THB4(B); \
 		break
 	if (elem_size != 4 && elem_size != 8) return CLO_HIP_EUNSUPPORTED;
+	if ((uintptr_t) dig % 16 != 0) {   // first digits fed at any byte: always one 8-bit digit per trip (radix 16 / 256)
+		if (bits != 8 || !c.big) return CLO_HIP_EUNSUPPORTED;
+		if (elem_size == 8) CLO_RW_THB1(8, 16, 1024, 2u, true); else CLO_RW_THB1(8, 32, 1024, 2u, true);
+		return (int) hipGetLastError();
+	}
 	switch (bits) {
 		CLO_RW_THB(1); CLO_RW_THB(2); CLO_RW_THB(3); CLO_RW_THB(4); CLO_RW_THB(5); CLO_RW_THB(6); CLO_RW_THB(7); CLO_RW_THB(8);
 		default: return CLO_HIP_EUNSUPPORTED;

@@ -587,7 +587,7 @@ size_t clo_hip_scan_workspace_bytes(size_t numel, int elem_size, int sum_size) {
 }
 
 int clo_hip_scan_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
-	if (!workspace || workspace_bytes < CLO_WS_HEADER_BYTES) return CLO_HIP_EARGS;
+	if (!workspace || clo_ws_misaligned(workspace) || workspace_bytes < CLO_WS_HEADER_BYTES) return CLO_HIP_EARGS;
 	const hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes, (hipStream_t) stream);
 	if (e != hipSuccess) return (int) e;
 	scan_ws_remember(workspace, workspace_bytes);
@@ -612,6 +612,7 @@ int clo_hip_scan_exclusive_carry(const void* data_in, void* data_out, size_t num
 	void* workspace, size_t workspace_bytes, void* stream) {
 
 	hipStream_t s = (hipStream_t) stream;
+	if (clo_misaligned(carry_in_dev, 8) || clo_misaligned(carry_out_dev, 8) || clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
 	if (numel == 0) {   // nothing to scan: the carry passes through
 		if (!carry_out_dev) return 0;
 		if (carry_in_dev) return (int) hipMemcpyAsync(carry_out_dev, carry_in_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s);
@@ -647,7 +648,7 @@ int clo_hip_scan_exclusive(const void* data_in, void* data_out, size_t numel,
 
 int clo_hip_reduce_sum(const void* data_in, size_t numel, int elem_size, int elem_signed,
 	uint64_t* total_dev, void* stream) {
-	if (!total_dev) return CLO_HIP_EARGS;
+	if (!total_dev || clo_misaligned(total_dev, 8)) return CLO_HIP_EARGS;
 	hipStream_t s = (hipStream_t) stream;
 	hipError_t e = hipMemsetAsync(total_dev, 0, sizeof(uint64_t), s);
 	if (e != hipSuccess) return (int) e;

@@ -29,6 +29,14 @@ extern "C" {
 #define CLO_HIP_ENOTREADY  (-5)  /* clo_hip_stream_query: work enqueued on the stream is still running */
 #define CLO_HIP_ERCCL      (-100) /* RCCL failures: CLO_HIP_ERCCL - ncclResult_t */
 
+/* Alignment. Data arrays (sources, destinations, keys, values, first digits) need only be aligned to their element
+ * size: a view into a larger allocation (a torch slice such as t[3:]) is fine, and kernels pick their vector loads
+ * from the pointers they are given. Scratch the kernels poll and count in is not: every `workspace` must start
+ * CLO_HIP_WORKSPACE_ALIGN bytes aligned (what hipMalloc and torch's allocator return), and every device uint64 word
+ * the kernels add to or hand over (carry_in_dev, carry_out_dev, total_dev, counts_dev) 8 bytes aligned. An entry
+ * given a misaligned one returns CLO_HIP_EARGS before anything is enqueued. */
+#define CLO_HIP_WORKSPACE_ALIGN 256
+
 /* ---- device / runtime (replaces ccl_context_*, ccl_queue_*, ccl_buffer_*,
  *      ccl_event_*, ccl_prof_* as used at sort/clo_sort_abstract.c:335-395,
  *      scan/clo_scan_abstract.c:290-339, benchmarks/clo_sort_bench.c:148-208) ---- */
@@ -157,7 +165,7 @@ int clo_hip_scan_exclusive_fp(const void* data_in, void* data_out, size_t numel,
 /* Sum of the elements mod 2^64 into *total_dev (device): what a shard hands
  * to the later shards of a multi-GPU scan. */
 int clo_hip_reduce_sum(const void* data_in, size_t numel, int elem_size, int elem_signed,
-	uint64_t* total_dev, void* stream);
+	uint64_t* total_dev, void* stream);   /* total_dev: 8-byte aligned */
 
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
@@ -186,8 +194,8 @@ int clo_hip_radix_sort(const void* src, void* dst, void* tmp, size_t numel,
 	int elem_size, int key_shift, int key_bits, int key_kind, int digit_bits,
 	void* workspace, size_t workspace_bytes, void* stream);
 /* The same sort FED by whoever produced the keys: first_digits[i] = the low 8 bits of element i's key field,
- * (elem[i] >> key_shift) & 0xff (device memory, numel bytes, read before anything is written — it may live in
- * `tmp`). The one re-read of the keys the sort has left is its first histogram; a producer that touches every
+ * (elem[i] >> key_shift) & 0xff (device memory, numel bytes at any byte address, read before anything is written —
+ * it may live in `tmp`). The one re-read of the keys the sort has left is its first histogram; a producer that touches every
  * key anyway (a key extractor, a generator, the pass before in a pipeline) writes those bytes for nearly nothing
  * and the histogram reads numel bytes instead of numel elements. clo_hip_radix_takes_first_digits says whether a
  * sort of this shape reads them (1: the chain-free passes on 16 384-element tiles, radix 16 or 256, unsigned
