@@ -10,6 +10,7 @@
 #include "clo_scan.h"
 #include "clo_sort.h"
 #include "clo_rng.h"
+#include "clo_reduce.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

@@ -167,6 +167,23 @@ int clo_hip_scan_exclusive_fp(const void* data_in, void* data_out, size_t numel,
 int clo_hip_reduce_sum(const void* data_in, size_t numel, int elem_size, int elem_signed,
 	uint64_t* total_dev, void* stream);   /* total_dev: 8-byte aligned */
 
+/* ---- reduce by key (new functionality: CloReduceByKey, include/clo_reduce.h) ----
+ * A run is a maximal stretch of consecutive elements whose keys (key_size 1, 2, 4 or 8 bytes) have the same bytes;
+ * with m runs, run r = [b_r, e_r): keys_out[r] = keys_in[b_r], aggr_out[r] = op over the run of (sum type) value,
+ * *num_runs_dev = m (device uint64, 8-byte aligned, required). Rows at index >= m are not written. op: 0 sum
+ * (wrap-around in the sum type), 1 min, 2 max (compared in the sum type). value_type / sum_type: CloType numbers, int,
+ * uint, long or ulong, the sum at least as wide as the value (anything else: CLO_HIP_EUNSUPPORTED). values_in NULL:
+ * every value is 1 (run lengths; sum only, value_type ignored). keys_out or aggr_out may be NULL (not written; without
+ * aggr_out neither values nor types are looked at), not both. No output range may overlap an input range. numel below
+ * 2^32; numel 0 sets *num_runs_dev and launches nothing. Three launches (tile sweep, scan of the tile states by one
+ * work-group, apply sweep), none of which waits for another work-group; asynchronous on `stream`.
+ * clo_hip_reduce_by_key_tile: the elements per tile for keys of key_size and values of value_size (0: none) bytes. */
+size_t clo_hip_reduce_by_key_tile(int key_size, int value_size);
+size_t clo_hip_reduce_by_key_workspace_bytes(size_t numel);
+int clo_hip_reduce_by_key(const void* keys_in, const void* values_in, void* keys_out, void* aggr_out, uint64_t* num_runs_dev,
+	size_t numel, int key_size, int value_type, int sum_type, int op,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
