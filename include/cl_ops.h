@@ -11,6 +11,7 @@
 #include "clo_sort.h"
 #include "clo_rng.h"
 #include "clo_reduce.h"
+#include "clo_scan_by_key.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

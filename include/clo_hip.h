@@ -184,6 +184,24 @@ int clo_hip_reduce_by_key(const void* keys_in, const void* values_in, void* keys
 	size_t numel, int key_size, int value_type, int sum_type, int op,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- scan by key (new functionality: CloScanByKey, include/clo_scan_by_key.h) ----
+ * Runs, op, value_type / sum_type and values_in NULL as for reduce by key above. With b(i) the first element of i's
+ * run: inclusive 1: out[i] = op over [b(i), i] of (sum type) value; inclusive 0: over [b(i), i), the identity at
+ * i = b(i) (0 for sum, the sum type's largest number for min, its smallest for max). Anything but 0 or 1 for
+ * `inclusive`, an op out of range, min / max without values, numel >= 2^32, a missing keys_in / out / workspace, a
+ * misaligned workspace or an `out` not aligned to its element: CLO_HIP_EARGS before anything is enqueued; types not built: CLO_HIP_EUNSUPPORTED; a workspace
+ * below clo_hip_scan_by_key_workspace_bytes(numel): CLO_HIP_EWORKSPACE. `out` may be exactly values_in when the sum
+ * type is as wide as the value type; no other overlap of out with an input is allowed (not checked here: the driver
+ * does). numel 0 launches nothing. Three launches (tile sweep, scan of the tile states by one work-group, apply
+ * sweep), none of which waits for another work-group; asynchronous on `stream`.
+ * clo_hip_scan_by_key_tile: the elements per tile for keys of key_size and values of value_size (0: none) bytes, 0
+ * for sizes not built. clo_hip_scan_by_key_workspace_bytes is monotone in numel. */
+size_t clo_hip_scan_by_key_tile(int key_size, int value_size);
+size_t clo_hip_scan_by_key_workspace_bytes(size_t numel);
+int clo_hip_scan_by_key(const void* keys_in, const void* values_in, void* out, size_t numel,
+	int key_size, int value_type, int sum_type, int op, int inclusive,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
