@@ -1,7 +1,7 @@
 /*
  * clo_oracle.c — CPU restatement of the cl_ops sort/scan hot path (see
- * clo_oracle.h for scope, citations and pin status: parity unpinned — the reference
- * holds no vectors for this path and cannot be run here). TEST INFRASTRUCTURE ONLY.
+ * clo_oracle.h for scope, citations and pin status: pinned by execution — tests/test_ref_pin.py
+ * compares it with upstream's own kernels run on the CPU). TEST INFRASTRUCTURE ONLY.
  *
  * Conventions: elements are handled as raw little-endian unsigned integers of
  * elem_size bytes (held in uint64_t). "ref:" comments name the upstream
@@ -38,6 +38,17 @@ static inline void st(void* base, size_t i, int es, uint64_t v) {
 		case 4: { uint32_t x = (uint32_t) v; memcpy(p, &x, 4); break; }
 		default: memcpy(p, &v, 8);
 	}
+}
+
+/* A scan element converted to the (wider or narrower) sum type as C converts integers:
+ * a signed element is sign-extended first (clo_scan_blelloch.cl:79-80, aux[lid] = data_in[..]). */
+static inline uint64_t ld_conv(const void* base, size_t i, int es, int is_signed) {
+	uint64_t v = ld(base, i, es);
+	if (is_signed && es < 8) {
+		int sh = 64 - 8 * es;
+		v = (uint64_t) ((int64_t) (v << sh) >> sh);
+	}
+	return v;
 }
 
 static inline uint64_t size_mask(int bytes) {
@@ -352,6 +363,16 @@ int clo_oracle_abitonic_mt(void* data, size_t numel, const clo_oracle_desc* d,
 	return launches;
 }
 
+void clo_oracle_abit_kernel(void* data, size_t n, const clo_oracle_desc* d, int family,
+	unsigned stage, unsigned step, unsigned S, size_t lws) {
+	switch (family) {
+		case 0: layer_any(data, n, stage, step, d, 1); break;
+		case 1: kernel_local(data, n, stage, step, lws, d, 1); break;
+		case 2: kernel_priv(data, n, stage, step, S, d, 1); break;
+		default: kernel_hyb(data, n, stage, step, S, lws, d, 1); break;
+	}
+}
+
 int clo_oracle_abitonic(void* data, size_t numel, const clo_oracle_desc* d,
 	size_t lws_max, size_t dev_max_lws,
 	unsigned minps, unsigned maxps, unsigned maxsfs) {
@@ -363,12 +384,12 @@ int clo_oracle_abitonic(void* data, size_t numel, const clo_oracle_desc* d,
 /* ------------------------------------------------------------------ */
 
 void clo_oracle_serial_scan(const void* data_in, void* data_out, size_t numel,
-	int elem_size, int sum_size) {
+	int elem_size, int elem_signed, int sum_size) {
 	/* ref: clo_scan_bench.c:252-271 — running sum compared element-wise. */
 	uint64_t acc = 0, m = size_mask(sum_size);
 	for (size_t i = 0; i < numel; ++i) {
 		st(data_out, i, sum_size, acc & m);
-		acc = (acc + ld(data_in, i, elem_size)) & m;
+		acc = (acc + ld_conv(data_in, i, elem_size, elem_signed)) & m;
 	}
 }
 
@@ -400,7 +421,7 @@ static uint64_t block_tree_scan(uint64_t* aux, size_t len, uint64_t m) {
 }
 
 static int blelloch_impl(const void* data_in, void* data_out, size_t numel,
-	int elem_size, int sum_size, size_t lws_max, size_t dev_max_lws, int threads) {
+	int elem_size, int elem_signed, int sum_size, size_t lws_max, size_t dev_max_lws, int threads) {
 
 	uint64_t m = size_mask(sum_size);
 	/* ref: clo_scan_blelloch.c:129-141 */
@@ -423,7 +444,7 @@ static int blelloch_impl(const void* data_in, void* data_out, size_t numel,
 		uint64_t in_sum = 0;
 		for (size_t b = 0; b < bpw && (wg * bpw + b) < nblocks; ++b) {
 			size_t g0 = (bpw * wg + b) * block;
-			for (size_t i = 0; i < block; ++i) aux[i] = ld(data_in, g0 + i, elem_size) & m;
+			for (size_t i = 0; i < block; ++i) aux[i] = ld_conv(data_in, g0 + i, elem_size, elem_signed) & m;
 			uint64_t prev = in_sum;
 			in_sum = (in_sum + block_tree_scan(aux, block, m)) & m;
 			for (size_t i = 0; i < block; ++i) st(data_out, g0 + i, sum_size, (aux[i] + prev) & m);
@@ -453,18 +474,18 @@ static int blelloch_impl(const void* data_in, void* data_out, size_t numel,
 }
 
 int clo_oracle_blelloch(const void* data_in, void* data_out, size_t numel,
-	int elem_size, int sum_size, size_t lws_max, size_t dev_max_lws) {
-	return blelloch_impl(data_in, data_out, numel, elem_size, sum_size, lws_max, dev_max_lws, 1);
+	int elem_size, int elem_signed, int sum_size, size_t lws_max, size_t dev_max_lws) {
+	return blelloch_impl(data_in, data_out, numel, elem_size, elem_signed, sum_size, lws_max, dev_max_lws, 1);
 }
 
 int clo_oracle_blelloch_mt(const void* data_in, void* data_out, size_t numel,
-	int elem_size, int sum_size, size_t lws, int threads) {
+	int elem_size, int elem_signed, int sum_size, size_t lws, int threads) {
 #ifdef _OPENMP
 	if (threads <= 0) threads = omp_get_max_threads();
 #else
 	threads = 1;
 #endif
-	blelloch_impl(data_in, data_out, numel, elem_size, sum_size, lws, lws, threads);
+	blelloch_impl(data_in, data_out, numel, elem_size, elem_signed, sum_size, lws, lws, threads);
 	return threads;
 }
 
@@ -581,7 +602,7 @@ static int satradix_impl(void* data, size_t numel, const clo_oracle_desc* d,
 		}
 
 		/* ---- scan of the counters, ref: satradix.c:298-299 ---- */
-		blelloch_impl(counters, counters_sum, naux, 4, 4, lws_max, dev_max_lws, threads);
+		blelloch_impl(counters, counters_sum, naux, 4, 0, 4, lws_max, dev_max_lws, threads);
 
 		if (pass == 0) {
 			if (dbg_offsets) memcpy(dbg_offsets, offsets, naux * sizeof(uint32_t));

@@ -11,15 +11,14 @@
  * element; here each kernel is restated as loops over work-groups/work-items
  * with the barriers turned into loop boundaries.
  *
- * Pin status: PARITY UNPINNED. The upstream tree holds NO golden vectors or unit tests for
- * sort/scan (only src/tests/test_rng.c). Its only known-answer checks for this
- * path are the benchmark self-checks (clo_sort_bench.c:211-226 adjacent-pair
- * order, clo_scan_bench.c:252-271 serial exclusive scan), restated below as
- * clo_oracle_check_sorted / clo_oracle_serial_scan; tests/test_oracle.py runs
- * every oracle algorithm through them and through independent stable-sort /
- * serial-scan references. The reference itself is unbuildable here (needs
- * cf4ocl2, GLib dev files and an OpenCL CPU device; none present) so the oracle
- * is NOT pinned against executed reference output.
+ * Pin status: PINNED BY EXECUTION. The upstream tree holds no golden vectors or unit
+ * tests for sort/scan (only src/tests/test_rng.c) and its host library cannot be built here, but
+ * its kernels can be run: oracle/ref_build.py compiles them for the host and tests/test_ref_pin.py
+ * compares every function below with them bit for bit. The launch loops and the work-size rule of
+ * cf4ocl2 remain restated. The reference's own known-answer checks (clo_sort_bench.c:211-226
+ * adjacent-pair order, clo_scan_bench.c:252-271 serial exclusive scan) are restated below as
+ * clo_oracle_check_sorted / clo_oracle_serial_scan; tests/test_oracle.py runs every oracle
+ * algorithm through them and through independent stable-sort / serial-scan references.
  */
 #ifndef CLO_ORACLE_H
 #define CLO_ORACLE_H
@@ -71,6 +70,12 @@ int clo_oracle_abitonic(void* data, size_t numel, const clo_oracle_desc* d,
 	size_t lws_max, size_t dev_max_lws,
 	unsigned minps, unsigned maxps, unsigned maxsfs);
 
+/* One launch of one abitonic kernel over the whole array, as the strategy above would issue it:
+ * family 0 abit_any (step), 1 abit_local_sK (step = K, lws), 2 abit_priv_SsVv (step, S),
+ * 3 abit_hyb_sK_SsVv (step = K, S, lws). For pinning each family against the executed kernel. */
+void clo_oracle_abit_kernel(void* data, size_t n, const clo_oracle_desc* d, int family,
+	unsigned stage, unsigned step, unsigned S, size_t lws);
+
 /* clo_sort_satradix.c:166-197,264-313 + clo_sort_satradix.cl:34-258, with the
  * scan step done by clo_oracle_blelloch (clo_sort_satradix.c:298). In place.
  * numel power of two. If dbg_offsets/dbg_counters/dbg_counters_sum are non-NULL
@@ -80,17 +85,18 @@ int clo_oracle_satradix(void* data, size_t numel, const clo_oracle_desc* d,
 	unsigned radix, size_t lws_max, size_t dev_max_lws,
 	uint32_t* dbg_offsets, uint32_t* dbg_counters, uint32_t* dbg_counters_sum);
 
-/* clo_scan_blelloch.c:129-195 + clo_scan_blelloch.cl:49-211. Exclusive scan,
- * elem_size -> sum_size widening, wrap-around in the sum type. Reference
+/* clo_scan_blelloch.c:129-195 + clo_scan_blelloch.cl:49-211. Exclusive scan of integer
+ * elements: each is converted to the sum type as C does (elem_signed: sign-extended when the
+ * sum is wider; low bits kept when it is narrower), wrap-around in the sum type. Reference
  * contract kept: the tail numel % (2*lws) is never scanned (blelloch.cl:70)
  * and data_out beyond the scanned blocks is left untouched. Returns launches. */
 int clo_oracle_blelloch(const void* data_in, void* data_out, size_t numel,
-	int elem_size, int sum_size, size_t lws_max, size_t dev_max_lws);
+	int elem_size, int elem_signed, int sum_size, size_t lws_max, size_t dev_max_lws);
 
 /* The reference's own known-answer checks. */
 /* clo_scan_bench.c:252-271: serial exclusive scan (sum type arithmetic). */
 void clo_oracle_serial_scan(const void* data_in, void* data_out, size_t numel,
-	int elem_size, int sum_size);
+	int elem_size, int elem_signed, int sum_size);
 /* clo_sort_bench.c:211-226 + clo_bench.c:26-65: returns index of first
  * adjacent pair out of order (typed compare of whole elements), or -1. */
 long clo_oracle_check_sorted(const void* data, size_t numel, int elem_size, int kind);
@@ -112,7 +118,7 @@ void clo_oracle_scan_bench_rand(uint32_t seed, int elem_size, void* out, size_t 
 int clo_oracle_satradix_mt(void* data, size_t numel, const clo_oracle_desc* d,
 	unsigned radix, size_t lws, int threads);
 int clo_oracle_blelloch_mt(const void* data_in, void* data_out, size_t numel,
-	int elem_size, int sum_size, size_t lws, int threads);
+	int elem_size, int elem_signed, int sum_size, size_t lws, int threads);
 /* The bitonic networks with the work-items of every launch (disjoint pairs, tiles) spread over
  * OpenMP threads: same bits as the serial versions. threads <= 0: all host cores. */
 void clo_oracle_sbitonic_mt(void* data, size_t numel, const clo_oracle_desc* d, int threads);

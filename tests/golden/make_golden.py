@@ -1,13 +1,16 @@
 """Generates tests/golden/*.npz — small input/expected-output vectors for the
 sort/scan hot path (SURVEY.md §8c "Fixtures to commit").
 
-The upstream tree holds no golden vectors for sort/scan and cannot be built or
-run in this image, so these vectors are NOT reference outputs: expected values
-are computed twice, by the CPU oracle (oracle/clo_oracle.c, which restates the
+The upstream tree holds no golden vectors for sort/scan. Expected values are
+computed twice, by the CPU oracle (oracle/clo_oracle.c, which restates the
 reference decomposition step by step) and by an independent numpy
 implementation (stable argsort / cumsum); the script refuses to write a vector
-on which the two disagree. The committed files pin both the oracle and the HIP
-path against regressions.
+on which the two disagree. They equal reference output too:
+tests/test_ref_pin.py runs upstream's own kernels (oracle/ref_build.py) on
+every input here whose shape upstream can run and demands these expected
+outputs, bit for bit. The committed files pin both the oracle and the HIP path
+against regressions; tests/golden/make_ref_golden.py records executed
+reference output directly.
 
 Run from the repo root:  python tests/golden/make_golden.py
 """

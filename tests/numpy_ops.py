@@ -4,6 +4,17 @@ tests and by `bench.py --dry-run` (a launcher test); the product only ever uses 
 import numpy as np
 
 
+def scan_cast_expected(a, sdt):
+    """Exclusive scan of `a` into sum type `sdt` as upstream's kernel defines it (clo_scan_blelloch.cl:79-80): every
+    element is converted with a C cast to the sum type (integers keep their low bits, floating-point values are
+    truncated toward zero) and added in that type, wrapping. tests/test_ref_pin.py holds this expression against the
+    executed upstream kernel; the GPU test of narrower and integer sums holds the HIP scanner against it."""
+    a, sdt = np.asarray(a), np.dtype(sdt)
+    cast = np.trunc(a.astype(np.float64)).astype(np.int64).astype(sdt) if np.issubdtype(a.dtype, np.floating) else a.astype(sdt)
+    wide = np.concatenate((np.zeros(1, np.uint64), np.cumsum(cast[:-1].astype(np.int64).astype(np.uint64), dtype=np.uint64)))
+    return wide.astype(np.dtype("u%d" % sdt.itemsize)).view(sdt)
+
+
 class NumpyLocalOps:
     """CPU stand-in for HipLocalOps with the same contract."""
 

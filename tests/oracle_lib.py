@@ -48,11 +48,13 @@ def lib():
         L.clo_oracle_gselect.restype = None
         L.clo_oracle_abitonic.argtypes = [vp, sz, C.POINTER(Desc), sz, sz, C.c_uint, C.c_uint, C.c_uint]
         L.clo_oracle_abitonic.restype = C.c_int
+        L.clo_oracle_abit_kernel.argtypes = [vp, sz, C.POINTER(Desc), C.c_int, C.c_uint, C.c_uint, C.c_uint, sz]
+        L.clo_oracle_abit_kernel.restype = None
         L.clo_oracle_satradix.argtypes = [vp, sz, C.POINTER(Desc), C.c_uint, sz, sz, vp, vp, vp]
         L.clo_oracle_satradix.restype = C.c_int
-        L.clo_oracle_blelloch.argtypes = [vp, vp, sz, C.c_int, C.c_int, sz, sz]
+        L.clo_oracle_blelloch.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, sz, sz]
         L.clo_oracle_blelloch.restype = C.c_int
-        L.clo_oracle_serial_scan.argtypes = [vp, vp, sz, C.c_int, C.c_int]
+        L.clo_oracle_serial_scan.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int]
         L.clo_oracle_serial_scan.restype = None
         L.clo_oracle_check_sorted.argtypes = [vp, sz, C.c_int, C.c_int]
         L.clo_oracle_check_sorted.restype = C.c_long
@@ -68,7 +70,7 @@ def lib():
         L.clo_oracle_abitonic_mt.restype = C.c_int
         L.clo_oracle_satradix_mt.argtypes = [vp, sz, C.POINTER(Desc), C.c_uint, sz, C.c_int]
         L.clo_oracle_satradix_mt.restype = C.c_int
-        L.clo_oracle_blelloch_mt.argtypes = [vp, vp, sz, C.c_int, C.c_int, sz, C.c_int]
+        L.clo_oracle_blelloch_mt.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, sz, C.c_int]
         L.clo_oracle_blelloch_mt.restype = C.c_int
         _lib = L
     return _lib
@@ -114,6 +116,14 @@ def abitonic(arr, lws_max=0, dev_max_lws=256, minps=1, maxps=4, maxsfs=0xFFFFFFF
     return out, launches
 
 
+def abit_kernel(arr, family, stage, step, S=1, lws=0, **kw):
+    """One launch of one abitonic kernel family (0 any, 1 local, 2 priv, 3 hyb) over the whole array."""
+    out = np.ascontiguousarray(arr).copy()
+    d = desc_for(out, **kw)
+    lib().clo_oracle_abit_kernel(_p(out), out.size, C.byref(d), family, stage, step, S, lws)
+    return out
+
+
 def satradix(arr, radix=16, lws_max=0, dev_max_lws=256, debug=False, threads=1, **kw):
     out = np.ascontiguousarray(arr).copy()
     d = desc_for(out, **kw)
@@ -142,14 +152,19 @@ def satradix(arr, radix=16, lws_max=0, dev_max_lws=256, debug=False, threads=1, 
     return out
 
 
+def _signed(a):
+    """Signed integer elements are sign-extended into a wider sum, as the C conversion of upstream's kernel does."""
+    return int(a.dtype.kind == "i")
+
+
 def blelloch(arr, sum_dtype, lws_max=0, dev_max_lws=256, threads=1):
     a = np.ascontiguousarray(arr)
     out = np.zeros(a.size, dtype=sum_dtype)
     if threads != 1:
-        lib().clo_oracle_blelloch_mt(_p(a), _p(out), a.size, a.dtype.itemsize, out.dtype.itemsize,
+        lib().clo_oracle_blelloch_mt(_p(a), _p(out), a.size, a.dtype.itemsize, _signed(a), out.dtype.itemsize,
                                      lws_max or dev_max_lws, threads)
     else:
-        lib().clo_oracle_blelloch(_p(a), _p(out), a.size, a.dtype.itemsize, out.dtype.itemsize,
+        lib().clo_oracle_blelloch(_p(a), _p(out), a.size, a.dtype.itemsize, _signed(a), out.dtype.itemsize,
                                   lws_max, dev_max_lws)
     return out
 
@@ -157,7 +172,7 @@ def blelloch(arr, sum_dtype, lws_max=0, dev_max_lws=256, threads=1):
 def serial_scan(arr, sum_dtype):
     a = np.ascontiguousarray(arr)
     out = np.zeros(a.size, dtype=sum_dtype)
-    lib().clo_oracle_serial_scan(_p(a), _p(out), a.size, a.dtype.itemsize, out.dtype.itemsize)
+    lib().clo_oracle_serial_scan(_p(a), _p(out), a.size, a.dtype.itemsize, _signed(a), out.dtype.itemsize)
     return out
 
 

@@ -54,12 +54,14 @@ def test_library_exports_nothing_but_the_declared_interface():
 def test_product_does_not_link_the_oracle():
     import subprocess
     out = subprocess.run(["nm", "-D", _hip.LIB_PATH], capture_output=True, text=True).stdout
-    assert "clo_oracle" not in out
+    assert "clo_oracle" not in out and "clo_ref" not in out
     src = ""
     for p in glob.glob(os.path.join(ROOT, "cl_ops_amd", "**", "*"), recursive=True):
         if os.path.isfile(p) and p.endswith((".py", ".c", ".h", ".hip")):
             src += open(p, errors="ignore").read()
     assert "oracle_lib" not in src and "libclo_oracle" not in src
+    # nor the executed reference (oracle/_ref, tests/ref_exec.py)
+    assert "ref_exec" not in src and "libclo_ref" not in src and "oracle/_ref" not in src and "clo_ref_" not in src
 
 
 def test_no_gpu_fails_loudly():

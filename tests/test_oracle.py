@@ -194,3 +194,66 @@ def test_typed_compare_matches_golden(name, kind):
     assert np.array_equal(O.gselect(a, key_kind=kind), exp)
     assert np.array_equal(O.sbitonic(a, key_kind=kind), exp)
     assert np.array_equal(O.abitonic(a, key_kind=kind)[0], exp)
+
+
+def test_restatements_against_recorded_outputs_of_the_executed_reference():
+    """tests/golden/ref_exec_golden.npz holds what upstream's own kernels gave (tests/golden/make_ref_golden.py; the
+    live comparison is tests/test_ref_pin.py, which needs the reference tree). Here the oracle and the RNG model are
+    held to those recordings, bit for bit, wherever the tree is absent too."""
+    import rng_model as M
+    R = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_exec_golden.npz"))
+    kind = {"i": O.KEY_SIGNED, "u": O.KEY_UNSIGNED, "f": O.KEY_FLOAT}
+    bits = lambda a: np.ascontiguousarray(a).view("u%d" % a.dtype.itemsize)
+    checked = 0
+    for name in R.files:
+        if name.startswith("keys_") and name.endswith("_in"):
+            a = R[name]
+            for tag, desc in (("asc", False), ("desc", True)):
+                exp = R[name[:-3] + "_" + tag]
+                kw = dict(key_kind=kind[a.dtype.kind], descending=desc)
+                assert np.array_equal(bits(O.sbitonic(a, **kw)), bits(exp)) and np.array_equal(bits(O.abitonic(a, **kw)[0]), bits(exp)), (name, tag)
+                g = name[:-3] + "_gselect_" + tag
+                assert np.array_equal(bits(O.gselect(a, **kw)), bits(R[g] if g in R.files else exp)), (name, tag)
+                checked += 3
+        elif name.startswith("tie_") and name.endswith("_in"):
+            p, key = R[name], name.split("_")[1]
+            for tag, desc in (("asc", False), ("desc", True)):
+                kw = dict(key_size=4, key_shift=32, key_kind=O.KEY_FLOAT if key == "float" else O.KEY_UNSIGNED, descending=desc)
+                assert np.array_equal(O.sbitonic(p, **kw), R["tie_%s_bitonic_%s" % (key, tag)]), (name, tag)
+                assert np.array_equal(O.abitonic(p, **kw)[0], R["tie_%s_bitonic_%s" % (key, tag)]), (name, tag)
+                g = R["tie_%s_gselect_%s" % (key, tag)]
+                assert np.array_equal(O.gselect(p[:g.size], **kw), g), (name, tag)
+                checked += 3
+        elif name.startswith("radix_") and name.endswith("_in"):
+            a = R[name]
+            for out in [f for f in R.files if f.startswith(name[:-3] + "_r")]:
+                radix = int(out.rsplit("_r", 1)[1])
+                assert np.array_equal(bits(O.satradix(a, radix=radix, dev_max_lws=64, key_kind=kind[a.dtype.kind])), bits(R[out])), out
+                checked += 1
+        elif name.startswith("scan_") and name.endswith("_in") and R[name].dtype.kind != "f":
+            a, exp = R[name], R[name[:-3] + "_out"]
+            assert np.array_equal(O.blelloch(a, exp.dtype, 0, 64), exp) and np.array_equal(O.serial_scan(a, exp.dtype), exp), name
+            checked += 1
+    assert np.array_equal(O.satradix(R["tie_uint_in"], dev_max_lws=64, key_size=4, key_shift=32), R["tie_uint_satradix"])
+    got = O.satradix(R["aux_in"], radix=16, lws_max=64, dev_max_lws=64, debug=True)
+    for g, what in zip(got, ("out", "offsets", "counters", "counters_sum")):
+        assert np.array_equal(g, R["aux_" + what]), what
+    S = 64
+    for tag in ("nohash", "knuth", "xs1", "ext"):
+        h, ms, nbits = str(R["rng_%s_hash" % tag]) or None, int(R["rng_%s_main_seed" % tag]), int(R["rng_%s_bits" % tag])
+        off = 0
+        for gi, gen in enumerate(M.NAMES):
+            nb = S * M.SEED_SIZE[gen]
+            seeds, fin = R["rng_%s_seeds" % tag][off:off + nb], R["rng_%s_final" % tag][off:off + nb]
+            off += nb
+            st = M.state_from_bytes(gen, seeds, S)
+            if tag != "ext":
+                assert np.array_equal(M.dev_gid_states(gen, S, ms, h), st), (gen, tag)
+            out, efin = M.fill(gen, st, S * 64, nbits)
+            assert np.array_equal(out, R["rng_%s_out" % tag][gi].reshape(-1)) and np.array_equal(efin, M.state_from_bytes(gen, fin, S)), (gen, tag)
+            checked += 1
+            if tag == "knuth":
+                for mi, maxint in enumerate(R["rng_maxints"]):
+                    assert np.array_equal(M.fill(gen, st, S * 4, 32, int(maxint))[0], R["rng_maxint_out"][gi, mi].reshape(-1)), (gen, maxint)
+                    checked += 1
+    assert checked >= 48 + 12 + 13 + 8 + 42, checked
