@@ -12,6 +12,7 @@
 #include "clo_rng.h"
 #include "clo_reduce.h"
 #include "clo_scan_by_key.h"
+#include "clo_histogram.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

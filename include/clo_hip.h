@@ -202,6 +202,30 @@ int clo_hip_scan_by_key(const void* keys_in, const void* values_in, void* out, s
 	int key_size, int value_type, int sum_type, int op, int inclusive,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- histogram (new functionality: CloHistogram, include/clo_histogram.h) ----
+ * Keys are integers of key_size (1, 2, 4, 8) bytes, two's complement when key_signed is not 0; `lower` holds the
+ * lower bound's bits in its low key_size bytes. With d = key - lower over the integers, an element is counted iff
+ * d >= 0 and (d >> shift) < num_bins, in bin d >> shift; hist_out[b] = sum over bin b's elements of (sum type) value,
+ * modulo 2^bits of the sum type. value_type / sum_type: CloType numbers, int, uint, long or ulong, the sum at least
+ * as wide as the value (anything else, and key sizes not built: CLO_HIP_EUNSUPPORTED). values_in NULL: every value is
+ * 1 (value_type ignored). accumulate 0: all num_bins entries are written (zeroed by a fill on `stream` first);
+ * otherwise the sums are added onto what hist_out holds. numel 0 launches no kernel. CLO_HIP_EARGS before anything
+ * is enqueued: hist_out NULL or not aligned to the sum type, num_bins 0 or >= 2^32, numel >= 2^32, shift >= 8 *
+ * key_size, keys_in NULL with numel > 0, keys or values not aligned to their element. hist_out must not overlap an
+ * input (not checked here: the driver does). max_groups: 0, or an upper bound on the work-groups launched (tests walk
+ * the grid-stride loop with 1, 2, 3). One launch of a fixed grid; no work-group waits for another; asynchronous on
+ * `stream`. The workspace may be NULL when clo_hip_histogram_workspace_bytes says 0 (it does today: every counter
+ * lives in LDS or in hist_out).
+ * clo_hip_histogram_tile: the elements per tile for keys of key_size and values of value_size (0: none) bytes, 0 for
+ * sizes not built. clo_hip_histogram_lds_bins: the largest num_bins whose counters a work-group keeps in LDS for sums
+ * of sum_size (4, 8) bytes, 0 for other sizes; above it the adds go straight to hist_out. */
+size_t clo_hip_histogram_tile(int key_size, int value_size);
+size_t clo_hip_histogram_lds_bins(int sum_size);
+size_t clo_hip_histogram_workspace_bytes(size_t numel, size_t num_bins);
+int clo_hip_histogram(const void* keys_in, const void* values_in, void* hist_out, size_t numel, int key_size, int key_signed,
+	int value_type, int sum_type, uint64_t lower, unsigned shift, size_t num_bins, int accumulate, unsigned max_groups,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
