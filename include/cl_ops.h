@@ -13,6 +13,7 @@
 #include "clo_reduce.h"
 #include "clo_scan_by_key.h"
 #include "clo_histogram.h"
+#include "clo_merge.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

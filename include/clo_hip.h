@@ -226,6 +226,32 @@ int clo_hip_histogram(const void* keys_in, const void* values_in, void* hist_out
 	int value_type, int sum_type, uint64_t lower, unsigned shift, size_t num_bins, int accumulate, unsigned max_groups,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- merge (new functionality: CloMerge, include/clo_merge.h) ----
+ * The stable merge of keys_a[0, numel_a) and keys_b[0, numel_b), each ascending, into keys_out[0, n), n = numel_a +
+ * numel_b: ties go to A, the order inside A and inside B is kept. Keys are key_size (1, 2, 4, 8) bytes and compare
+ * by key_kind: 0 unsigned, 1 signed (two's complement), 2 IEEE total order (2, 4, 8 bytes). value_size 0: keys only.
+ * value_size 4 or 8: values_out[j] is the value of the element at keys_out[j]; with value_size 4 and the values of
+ * every non-empty input NULL it is that element's index in A || B instead (argmerge: i for A[i], numel_a + i for
+ * B[i]). keys_out may be NULL when values_out is given. The values pointer of an empty input is not looked at.
+ * CLO_HIP_EARGS before anything is enqueued: key_kind out of range, n >= 2^32, NULL keys of a non-empty input, both
+ * outputs NULL, values (in or out) with value_size 0, values_out NULL with value_size > 0, values given for one
+ * non-empty input and NULL for the other, NULL values with value_size 8, a pointer not aligned to its element, a
+ * missing or misaligned workspace. Sizes not built: CLO_HIP_EUNSUPPORTED. A workspace below
+ * clo_hip_merge_workspace_bytes(numel_a, numel_b): CLO_HIP_EWORKSPACE. No output may overlap an input or the other
+ * output (not checked here: the driver does). n 0 launches nothing and needs no workspace. On inputs that are not
+ * sorted the outputs' contents are unspecified; reads stay inside the inputs and writes inside [0, n) of the outputs.
+ * Two launches (the tiles' split points into the workspace, then one work-group per tile of the output); no work-group
+ * waits for another; asynchronous on `stream`; nothing is allocated and the host never waits, so the call can be
+ * captured into a graph.
+ * clo_hip_merge_tile: the output elements per tile for keys of key_size and values of value_size (0: none) bytes, 0
+ * for sizes not built. clo_hip_merge_workspace_bytes is monotone in numel_a + numel_b and 0 for n = 0. */
+size_t clo_hip_merge_tile(int key_size, int value_size);
+size_t clo_hip_merge_workspace_bytes(size_t numel_a, size_t numel_b);
+int clo_hip_merge(const void* keys_a, const void* values_a, size_t numel_a,
+	const void* keys_b, const void* values_b, size_t numel_b,
+	void* keys_out, void* values_out, int key_size, int key_kind,
+	int value_size, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
