@@ -1,0 +1,271 @@
+"""The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram and CloMerge on the queue production uses (no
+profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace belongs to one
+queue at a time"): one object is called six times on two live queues in turn, with no host synchronisation between the
+calls and sizes that make it reuse and outgrow its workspace mid-sequence; then the queue of its last call is destroyed
+and the object is used on a third one, through the host-data and the device form. Last, the whole group-by pipeline
+(sort by key -> scan by key -> reduce by key -> histogram of the reduced keys -> merge of two such outputs) runs on one
+non-profiling queue without a finish() until the end, and gives the bits of the same pipeline on the session's
+profiling queue and of numpy. The results are compared, not the interleavings; everything is exact."""
+import numpy as np
+import pytest
+
+from hist_model import histogram
+from merge_model import merge, order_key
+from rbk_model import rbk
+from sbk_model import sbk
+from test_gpu_reduce_by_key import structure, make_keys, make_values
+
+pytestmark = pytest.mark.gpu
+
+BIG = (1 << 22) + 3
+SIZES = [4099, BIG, 3001, BIG, 5003, BIG + 8192]      # outgrown at the second call, reused small and large, outgrown again
+LOWER, SHIFT, BINS = 1000, 2, 4096
+
+
+class _SortByKey:
+    """ushort keys, uint values carried along. Arrays: (keys, values) -> (keys_out, values_out)."""
+    out_types = (np.uint16, np.uint32)
+
+    def new(self, clo, ctx):
+        return clo.Sorter("satradix", ctx, "ushort")
+
+    def inputs(self, n, seed):
+        rng = np.random.default_rng(seed)
+        return rng.integers(0, 1 << 16, n, dtype=np.uint16), rng.integers(0, 1 << 32, n, dtype=np.uint32)
+
+    def out_counts(self, ins):
+        return ins[0].size, ins[0].size
+
+    def call(self, obj, q, i, o, ins):
+        return obj.by_key_with_device_data(q, i[0], i[1], o[0], o[1], ins[0].size)
+
+    def want(self, ins):
+        order = np.argsort(order_key(ins[0]), kind="stable")
+        return ins[0][order], ins[1][order]
+
+    def host(self, obj, q, ins):
+        return obj.by_key_with_host_data(ins[0], ins[1], q_exec=q)
+
+
+class _ReduceByKey:
+    """uint keys in runs of 100 on average, uint values summed in ulong. -> (keys_out, aggr_out, the run count)."""
+    out_types = (np.uint32, np.uint64, np.uint64)
+
+    def new(self, clo, ctx):
+        return clo.ReduceByKey(ctx, "uint", "uint", "ulong")
+
+    def inputs(self, n, seed):
+        return make_keys("uint", structure("geo100", n, 0, seed=seed), seed=seed % 7), make_values("uint", n, seed)
+
+    def out_counts(self, ins):
+        return ins[0].size, ins[0].size, 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], i[1], o[0], o[1], o[2], ins[0].size)
+
+    def want(self, ins):
+        wk, wa, m = rbk(ins[0], ins[1], "sum", np.uint64)
+        return wk, wa, np.array([m], np.uint64)
+
+    def host(self, obj, q, ins):
+        ko, ao = obj.with_host_data(ins[0], ins[1], q_exec=q)
+        return ko, ao, np.array([ko.size], np.uint64)
+
+
+class _ScanByKey(_ReduceByKey):
+    """The same inputs; the exclusive running sum in uint (it wraps)."""
+    out_types = (np.uint32,)
+
+    def new(self, clo, ctx):
+        return clo.ScanByKey(ctx, "uint", "uint", "uint")
+
+    def out_counts(self, ins):
+        return (ins[0].size,)
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], i[1], o[0], ins[0].size)
+
+    def want(self, ins):
+        return (sbk(ins[0], ins[1], "sum", np.uint32, False),)
+
+    def host(self, obj, q, ins):
+        return (obj.with_host_data(ins[0], ins[1], q_exec=q),)
+
+
+class _Histogram:
+    """uint keys, a tenth of them outside the range, uint values summed in ulong per bin."""
+    out_types = (np.uint64,)
+
+    def new(self, clo, ctx):
+        return clo.Histogram(ctx, "uint", "uint", "ulong")
+
+    def inputs(self, n, seed):
+        rng = np.random.default_rng(seed)
+        return (rng.integers(LOWER - 500, LOWER + (BINS << SHIFT) + 1200, n, dtype=np.int64).astype(np.uint32),
+                rng.integers(0, 1 << 32, n, dtype=np.uint32))
+
+    def out_counts(self, ins):
+        return (BINS,)
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], i[1], o[0], ins[0].size, lower=LOWER, shift=SHIFT, num_bins=BINS)
+
+    def want(self, ins):
+        return (histogram(ins[0], ins[1], np.uint64, LOWER, SHIFT, BINS),)
+
+    def host(self, obj, q, ins):
+        return (obj.with_host_data(ins[0], ins[1], lower=LOWER, shift=SHIFT, num_bins=BINS, q_exec=q),)
+
+
+class _Merge:
+    """n ushort keys in A and a third as many in B, many ties inside and across; uint values = the source index."""
+    out_types = (np.uint16, np.uint32)
+
+    def new(self, clo, ctx):
+        return clo.Merge(ctx, "ushort", 4)
+
+    def inputs(self, n, seed):
+        rng = np.random.default_rng(seed)
+        na, nb = n - n // 3, n // 3
+        v = np.arange(n, dtype=np.uint32)
+        return np.sort(rng.integers(0, 5000, na).astype(np.uint16)), v[:na], np.sort(rng.integers(0, 5000, nb).astype(np.uint16)), v[na:]
+
+    def out_counts(self, ins):
+        return ins[0].size + ins[2].size, ins[0].size + ins[2].size
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], i[1], ins[0].size, i[2], i[3], ins[2].size, o[0], o[1])
+
+    def want(self, ins):
+        wk, p = merge(ins[0], ins[2])
+        return wk, np.concatenate((ins[1], ins[3]))[p]
+
+    def host(self, obj, q, ins):
+        return obj.with_host_data(ins[0], ins[2], ins[1], ins[3], q_exec=q)
+
+
+def _same(got, want, what):
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g.dtype.itemsize == w.dtype.itemsize and np.array_equal(np.asarray(g).view(np.uint8), np.asarray(w).view(np.uint8)), \
+            "%s: output %d differs from the model" % (what, k)
+
+
+@pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge], ids=lambda k: k.__name__.strip("_"))
+def test_object_moves_between_queues(gpu, kind):
+    import cl_ops_amd as clo
+    ctx, _ = gpu
+    k = kind()
+    q1, q2 = clo.Queue(ctx), clo.Queue(ctx)               # no profiling: the queues production uses
+    obj = k.new(clo, ctx)
+    calls = []
+    for c, n in enumerate(SIZES):                          # fresh inputs and outputs for every call, all there before the first
+        ins = k.inputs(n, 100 + c)
+        dev_in = [clo.Buffer(ctx, max(a.nbytes, 16)) for a in ins]
+        for b, a in zip(dev_in, ins):
+            b.write(q1, a)
+        dev_out = [clo.Buffer(ctx, max(cnt * np.dtype(t).itemsize, 16)) for cnt, t in zip(k.out_counts(ins), k.out_types)]
+        calls.append((ins, dev_in, dev_out))
+    q1.finish()
+    for c, (ins, dev_in, dev_out) in enumerate(calls):     # six calls back to back, the queues in turn
+        assert k.call(obj, (q1, q2)[c % 2], dev_in, dev_out, ins)
+    q1.finish()
+    q2.finish()
+    for c, (ins, dev_in, dev_out) in enumerate(calls):
+        want = k.want(ins)
+        got = [b.read(q1, t, w.size) for b, t, w in zip(dev_out, k.out_types, want)]
+        _same(got, want, "call %d of %d elements on queue %d" % (c, SIZES[c], 1 + c % 2))
+        same_in = [b.read(q1, a.dtype, a.size) for b, a in zip(dev_in, ins)]
+        _same(same_in, ins, "call %d: the inputs" % c)
+        for b in dev_in + dev_out:
+            b.close()
+    q2.close()                                             # the object's last call ran on q2: it remembers a queue that is gone
+    q3 = clo.Queue(ctx)
+    ins = k.inputs(BIG, 200)
+    _same(k.host(obj, q3, ins), k.want(ins), "host data on a third queue")
+    ins = k.inputs(70001, 201)
+    dev_in = [clo.Buffer(ctx, a.nbytes) for a in ins]
+    for b, a in zip(dev_in, ins):
+        b.write(q3, a)
+    want = k.want(ins)
+    dev_out = [clo.Buffer(ctx, max(cnt * np.dtype(t).itemsize, 16)) for cnt, t in zip(k.out_counts(ins), k.out_types)]
+    assert k.call(obj, q3, dev_in, dev_out, ins)
+    q3.finish()
+    _same([b.read(q3, t, w.size) for b, t, w in zip(dev_out, k.out_types, want)], want, "device data on a third queue")
+    for x in dev_in + dev_out + [obj, q1, q3]:
+        x.close()
+
+
+N_PIPE, DISTINCT = (1 << 20) + 3, 700
+
+
+def _pipeline_inputs(seed):
+    """N_PIPE uint keys from DISTINCT values, every one of them present (so that the number of rows of the reduce by
+    key is known to the host without a look at the device), and uint values."""
+    rng = np.random.default_rng(seed)
+    pool = np.sort(rng.choice(1 << 16, DISTINCT, replace=False)).astype(np.uint32)
+    keys = pool[rng.integers(0, DISTINCT, N_PIPE)]
+    keys[rng.permutation(N_PIPE)[:DISTINCT]] = pool
+    return keys, rng.integers(0, 1 << 32, N_PIPE, dtype=np.uint32)
+
+
+def _pipeline_model(keys, values):
+    order = np.argsort(keys, kind="stable")
+    sk, sv = keys[order], values[order]
+    running = sbk(sk, sv, "sum", np.uint32, True)
+    rk, ra, m = rbk(sk, sv, "sum", np.uint32)
+    assert m == DISTINCT
+    return [sk, sv, running, rk, ra, np.array([m], np.uint64), histogram(rk, None, np.uint32, 0, 8, 256)]
+
+
+def _run_pipeline(clo, ctx, q, inputs):
+    """Both inputs through sort by key -> scan by key -> reduce by key -> histogram, then the merge of the two reduced
+    tables; nothing waits for the device before the last call is enqueued. Returns every intermediate array."""
+    n = N_PIPE
+    B = lambda nbytes: clo.Buffer(ctx, nbytes)
+    s, sc = clo.Sorter("satradix", ctx, "uint"), clo.ScanByKey(ctx, "uint", "uint", "uint", inclusive=True)
+    r, h, mg = clo.ReduceByKey(ctx, "uint", "uint", "uint"), clo.Histogram(ctx, "uint", None, "uint"), clo.Merge(ctx, "uint", 4)
+    sides, bufs = [], []
+    for keys, values in inputs:
+        d = dict(kin=B(4 * n), vin=B(4 * n), sk=B(4 * n), sv=B(4 * n), run=B(4 * n), rk=B(4 * n), ra=B(4 * n), cnt=B(8), hist=B(4 * 256))
+        d["kin"].write(q, keys)
+        d["vin"].write(q, values)
+        sides.append(d)
+        bufs += list(d.values())
+    mk, mv = B(4 * 2 * DISTINCT), B(4 * 2 * DISTINCT)
+    q.finish()
+    for d in sides:
+        assert s.by_key_with_device_data(q, d["kin"], d["vin"], d["sk"], d["sv"], n)
+        assert sc.with_device_data(q, d["sk"], d["sv"], d["run"], n)
+        assert r.with_device_data(q, d["sk"], d["sv"], d["rk"], d["ra"], d["cnt"], n)
+        assert h.with_device_data(q, d["rk"], None, d["hist"], DISTINCT, lower=0, shift=8, num_bins=256)
+    a, b = sides
+    assert mg.with_device_data(q, a["rk"], a["ra"], DISTINCT, b["rk"], b["ra"], DISTINCT, mk, mv)
+    q.finish()
+    got = []
+    for d in sides:
+        got.append([d["sk"].read(q, np.uint32, n), d["sv"].read(q, np.uint32, n), d["run"].read(q, np.uint32, n), d["rk"].read(q, np.uint32, DISTINCT),
+                    d["ra"].read(q, np.uint32, DISTINCT), d["cnt"].read(q, np.uint64, 1), d["hist"].read(q, np.uint32, 256)])
+    got.append([mk.read(q, np.uint32, 2 * DISTINCT), mv.read(q, np.uint32, 2 * DISTINCT)])
+    for x in bufs + [mk, mv, s, sc, r, h, mg]:
+        x.close()
+    return got
+
+
+def test_group_by_pipeline_on_a_non_profiling_queue(gpu):
+    import cl_ops_amd as clo
+    ctx, q_prof = gpu
+    inputs = [_pipeline_inputs(31), _pipeline_inputs(32)]
+    want = [_pipeline_model(*i) for i in inputs]
+    wk, p = merge(want[0][3], want[1][3])
+    want.append([wk, np.concatenate((want[0][4], want[1][4]))[p]])
+    q = clo.Queue(ctx)
+    plain = _run_pipeline(clo, ctx, q, inputs)
+    q.close()
+    prof = _run_pipeline(clo, ctx, q_prof, inputs)
+    names = ["sorted keys", "sorted values", "running sums", "reduced keys", "sums per key", "run count", "histogram of the reduced keys"]
+    for side, (g1, g2, w) in enumerate(zip(plain, prof, want)):
+        for k, (x1, x2, y) in enumerate(zip(g1, g2, w)):
+            what = "merge output %d" % k if side == 2 else "input %d, %s" % (side, names[k])
+            assert x1.dtype == y.dtype and np.array_equal(x1, y), what + ": the non-profiling queue differs from numpy"
+            assert np.array_equal(x1, x2), what + ": the two queues differ"

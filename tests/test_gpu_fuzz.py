@@ -1,11 +1,24 @@
 """Seeded random sweeps over the sort / scan entry points (GPU): sizes that straddle
 every path boundary (one-launch sorts, single-sweep passes, 8 192- and 16 384-element
 tiles), every radix, element types, in place / out of place, stable pairs — against
-numpy. Everything goes through the C-ABI of libcl_ops_hip.so."""
+numpy. Everything goes through the C-ABI of libcl_ops_hip.so.
+
+The second half is the STRATIFIED fuzz of reduce by key, scan by key, histogram and merge: the kernels of those four
+are templates over (key size x value -> sum conversion x op or mode), and draw_cases() walks the list of those
+instantiations, written out below from the public type rules, so that the committed seeds together launch every one;
+sizes, run structures, bounds, layouts, view offsets and the reuse of one object over a random sequence of sizes are
+random per case. draw_cases() and the *_inputs() functions touch no GPU: tests/test_fuzz_reach_cpu.py imports them."""
+import math
+
 import numpy as np
 import pytest
 
 import oracle_lib as O
+import sbk_model
+import test_gpu_histogram as TH
+import test_gpu_merge as TM
+import test_gpu_reduce_by_key as TR
+import test_gpu_scan_by_key as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -230,3 +243,363 @@ def test_fuzz_sharded_sort_loopback(gpu, seed):
             assert m == n, (etype, opt, mode, n)
             assert np.array_equal(out.cpu().numpy().view(dt)[:n], np.sort(a)), (etype, opt, mode, n)
         s.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The stratified fuzz of the four by-key families
+# ----------------------------------------------------------------------------------------------------------------------
+
+_KT_BY_SIZE = {1: ["uchar"], 2: ["ushort"], 4: ["uint", "int", "float"], 8: ["ulong", "double"]}     # reduce / scan by key
+_BK_PAIRS = [("uint", "uint"), ("int", "long"), ("uint", "ulong"), ("ulong", "ulong")]
+_BK_KINDS = ["len_uint", "len_ulong"] + [(vt, st, op) for vt, st in _BK_PAIRS for op in ("sum", "min", "max")]
+_HIST_KT = {(1, 0): "uchar", (1, 1): "char", (2, 0): "ushort", (2, 1): "short", (4, 0): "uint", (4, 1): "int", (8, 0): "ulong", (8, 1): "long"}
+_HIST_CVT = {"cnt_uint": (None, "uint"), "cnt_ulong": (None, "ulong"), "uint->uint": ("uint", "uint"), "int->long": ("int", "long"),
+             "uint->ulong": ("uint", "ulong"), "long->long": ("long", "long")}
+_HIST_BINS = ["copies", "peel", "global"]      # <= the 32-copy limit | up to histogram_lds_bins | histogram_lds_bins + 1
+_MERGE_MODES = ["keys", "v4", "v8", "arg", "arg_only"]
+
+# Every kernel instantiation a family has, from the public type rules (include/clo_reduce.h, clo_scan_by_key.h,
+# clo_histogram.h, clo_merge.h; DESIGN.md for the three forms of the histogram), not from the kernels' enums.
+STRATA = {
+    "rbk": [(ks, kind) for ks in (1, 2, 4, 8) for kind in ["keys_only"] + _BK_KINDS],
+    "sbk": [(ks, kind, incl) for ks in (1, 2, 4, 8) for kind in _BK_KINDS for incl in (False, True)],
+    "hist": [(ks, sg, cvt, b) for ks in (1, 2, 4, 8) for sg in (0, 1) for cvt in _HIST_CVT for b in _HIST_BINS],
+    "merge": [(kt, mode) for kt in TM.KEY_TYPES for mode in _MERGE_MODES],
+}
+# seeds x cases >= 2 x strata: half the cases of a seed open a new stratum (with a new object), the other half reuse
+# the object of the case before them on a stratum it can run
+SEEDS = {"rbk": 2, "sbk": 3, "hist": 4, "merge": 2}
+CASES = {"rbk": 60, "sbk": 76, "hist": 72, "merge": 60}
+_SALT = {"rbk": 61, "sbk": 62, "hist": 63, "merge": 64}
+
+
+def _size(x):
+    return np.dtype(x).itemsize
+
+
+def _vsize(family, vt):
+    return 0 if vt is None else _size((TH._NP if family == "hist" else TR._NP)[vt])
+
+
+def tile_of(family, ks, vs):
+    """Elements per tile, from the library's getters (host code only)."""
+    import cl_ops_amd as clo
+    t = {"rbk": clo.reduce_by_key_tile, "sbk": clo.scan_by_key_tile, "hist": clo.histogram_tile, "merge": clo.merge_tile}[family](ks, vs)
+    assert t > 0
+    return int(t)
+
+
+def hist_limits(ss):
+    """(the largest num_bins with 32 LDS copies: num_bins * 32 * ss <= 32 KiB, the largest with counters in LDS)."""
+    import cl_ops_amd as clo
+    L = int(clo.histogram_lds_bins(ss))
+    assert L > 256
+    return (32 << 10) // (32 * ss), L
+
+
+_EDGE_SIZES = [lambda t: 0, lambda t: 1, lambda t: t - 1, lambda t: t, lambda t: t + 1, lambda t: 2 * t - 1, lambda t: 2 * t + 1, lambda t: 3 * t + 1]
+
+
+def _draw_n(rng, tile, edge=None):
+    """Mostly below 4 tiles, a tail up to about 2^20, never only tile multiples. edge: one of _EDGE_SIZES instead
+    (every seed deals each of them to one of its cases, whatever that case's tile is)."""
+    if edge is not None:
+        return _EDGE_SIZES[edge](tile)
+    u = rng.random()
+    if u < 0.15:
+        return int(rng.integers(2, 600))              # a few waves of one work-group
+    if u < 0.8:
+        return int(rng.integers(2, 4 * tile))
+    return int(2.0 ** rng.uniform(math.log2(4 * tile), 20.0)) + int(rng.integers(0, 7))
+
+
+def _draw_off(rng, es):
+    """An element-aligned byte offset in 0 .. 31."""
+    return 0 if not es else int(es * rng.integers(0, 32 // es))
+
+
+def _draw_structure(rng, n, tile):
+    """A mixture of geometric stretches (each with a mean of its own from 1 to 50 000), sometimes unsorted key numbers,
+    and one run longer than two tiles where n allows it."""
+    s = {"kind": "unsorted" if rng.random() < 0.15 else "mixture", "seed": int(rng.integers(0, 1 << 30)), "cuts": [], "means": [], "long": None}
+    if s["kind"] == "mixture":
+        parts = int(rng.integers(1, 5))
+        s["cuts"] = sorted(int(x) for x in rng.integers(0, n + 1, parts - 1))
+        s["means"] = [max(1, int(50000.0 ** rng.random())) for _ in range(parts)]
+    if n > 2 * tile + 1:
+        ln = 2 * tile + 1 + int(rng.integers(0, min(tile, n - 2 * tile - 1) + 1))
+        s["long"] = (int(rng.integers(0, n - ln + 1)), ln)
+    return s
+
+
+def _object_for(family, rng, stratum):
+    """The constructor arguments of a new object that can run the stratum."""
+    if family in ("rbk", "sbk"):
+        kt = str(rng.choice(_KT_BY_SIZE[stratum[0]]))
+        kind = stratum[1]
+        if kind == "keys_only":
+            vt, st = _BK_PAIRS[int(rng.integers(0, 4))]
+            op = str(rng.choice(["sum", "min", "max"]))
+        elif kind == "len_uint":
+            vt, st, op = "uint", "uint", "sum"
+        elif kind == "len_ulong":
+            vt, st, op = [("uint", "ulong"), ("ulong", "ulong")][int(rng.integers(0, 2))] + ("sum",)
+        else:
+            vt, st, op = kind
+        return (kt, vt, st, op) if family == "rbk" else (kt, vt, st, op, stratum[2])
+    if family == "hist":
+        vt, st = _HIST_CVT[stratum[2]]
+        return (_HIST_KT[stratum[:2]], vt or "uint", st, bool(rng.integers(0, 2)))
+    return (stratum[0], TM._VS[stratum[1]])
+
+
+def compatible(family, obj):
+    """The strata an object can run."""
+    if family in ("rbk", "sbk"):
+        kt, vt, st, op = obj[:4]
+        ks = _size(TR._NP[kt])
+        kinds = [(vt, st, op)] + (["len_" + st] if op == "sum" and st in ("uint", "ulong") else [])
+        if family == "rbk":
+            return [(ks, k) for k in ["keys_only"] + kinds]
+        return [(ks, k, obj[4]) for k in kinds]
+    if family == "hist":
+        kt, vt, st, _ = obj
+        key = [k for k, v in _HIST_KT.items() if v == kt][0]
+        cvts = [c for c, p in _HIST_CVT.items() if p == (vt, st)] + (["cnt_" + st] if st in ("uint", "ulong") else [])
+        return [key + (c, b) for c in cvts for b in _HIST_BINS]
+    return [(obj[0], m) for m in _MERGE_MODES if TM._VS[m] == obj[1]]
+
+
+def _draw_call(family, rng, stratum, obj, edge=None):
+    """Everything of one call but the object: plain numbers, strings and lists."""
+    c = {}
+    if family in ("rbk", "sbk"):
+        kt, vt, st, op = obj[:4]
+        kind = stratum[1]
+        given = None if kind in ("len_uint", "len_ulong") else vt
+        if kind == "keys_only" and op == "sum" and rng.random() < 0.5:
+            given = None                                   # the keys alone, from a call without values too (min / max need them)
+        ks, vs, ss = _size(TR._NP[kt]), _vsize(family, given), _size(TR._NP[st])
+        tile = tile_of(family, ks, vs)
+        n = _draw_n(rng, tile, edge)
+        c.update(kt=kt, vt=given, st=st, op=op, n=n, tile=tile, structure=_draw_structure(rng, n, tile),
+                 palette_seed=int(rng.integers(0, 50)), value_seed=int(rng.integers(0, 1 << 30)))
+        if family == "rbk":
+            c.update(want_k=bool(kind == "keys_only" or rng.random() < 0.8), want_a=kind != "keys_only",
+                     offs=[_draw_off(rng, ks), _draw_off(rng, vs or 4), _draw_off(rng, ks), _draw_off(rng, ss)])
+        else:
+            c.update(inclusive=obj[4], in_place=bool(given is not None and vs == ss and rng.random() < 0.2),
+                     offs=[_draw_off(rng, ks), _draw_off(rng, vs or 4), _draw_off(rng, ss)])
+    elif family == "hist":
+        kt, vt, st, acc = obj
+        given = None if stratum[2].startswith("cnt_") else vt
+        info = np.iinfo(TH._NP[kt])
+        ks, vs, ss = info.bits // 8, _vsize(family, given), _size(TH._NP[st])
+        tile = tile_of(family, ks, vs)
+        copies, L = hist_limits(ss)
+        nb = {"copies": int(rng.integers(1, copies + 1)), "peel": int(rng.choice([copies + 1, int(rng.integers(copies + 1, L + 1)), L])),
+              "global": L + 1}[stratum[3]]
+        shift = int(rng.integers(0, 4)) if rng.random() < 0.5 else int(rng.integers(0, info.bits))
+        u = rng.random()
+        lo, hi = int(info.min), int(info.max)
+        if u < 0.3:          # within num_bins << shift of the type's maximum: the wrap trap
+            lower = hi - int(rng.integers(0, min(nb << shift, hi - lo) + 1, dtype=np.uint64))
+        elif u < 0.4:
+            lower = lo
+        else:
+            lower = lo + int(rng.integers(0, hi - lo, dtype=np.uint64, endpoint=True))
+        layout = str(rng.choice(["uniform", "skewed", "sorted", "handful"]))
+        c.update(kt=kt, vt=given, st=st, accumulate=acc, n=_draw_n(rng, tile, edge), tile=tile, num_bins=nb, shift=shift, lower=lower, layout=layout,
+                 outside=0.0 if layout == "sorted" else float(rng.choice([0.0, 0.2])), data_seed=int(rng.integers(0, 1 << 30)),
+                 offs=[_draw_off(rng, ks), _draw_off(rng, vs or 4), _draw_off(rng, ss)])
+    else:
+        kt, vs = obj
+        mode = stratum[1]
+        ks = _size(TM._NP[kt])
+        tile = tile_of(family, ks, vs)
+        na, nb = (0 if rng.random() < 0.08 else _draw_n(rng, tile) for _ in range(2))
+        if edge is not None:
+            na, nb = [(_draw_n(rng, tile, edge), nb), (na, _draw_n(rng, tile, edge))][int(rng.integers(0, 2))]
+        if na + nb == 0:     # (both empty: test_gpu_merge.py's test_both_empty)
+            nb = 1
+        has_v, has_k = mode in ("v4", "v8"), mode != "arg_only"
+        c.update(kt=kt, mode=mode, na=na, nb=nb, tile=tile, ranges=str(rng.choice(["overlapping", "a_below_b", "b_below_a", "interleaved"])),
+                 data_seed=int(rng.integers(0, 1 << 30)),
+                 offs=[_draw_off(rng, ks), _draw_off(rng, vs if has_v else 0), _draw_off(rng, ks), _draw_off(rng, vs if has_v else 0),
+                       _draw_off(rng, ks if has_k else 0), _draw_off(rng, vs)])
+    return c
+
+
+def draw_cases(family, seed):
+    """The cases of one seed as plain descriptions. The seed's share of the family's strata (the list, shuffled once, is
+    dealt to the seeds in turn) is walked in order, each with a new object; between them, at random places, as many cases
+    again reuse the object of the case before on a random stratum it can run, with a size of their own."""
+    strata = STRATA[family]
+    order = np.random.default_rng(_SALT[family]).permutation(len(strata))
+    share = -(-len(strata) // SEEDS[family])
+    mine = [strata[int(order[(seed * share + k) % len(strata)])] for k in range(share)]
+    total = CASES[family]
+    assert 0 <= seed < SEEDS[family] and total >= share
+    rng = np.random.default_rng([_SALT[family], seed])
+    fresh = np.zeros(total, bool)
+    fresh[0] = True
+    fresh[1 + rng.permutation(total - 1)[:share - 1]] = True
+    edges = dict(zip((int(x) for x in rng.permutation(total)[:len(_EDGE_SIZES)]), range(len(_EDGE_SIZES))))
+    cases, obj, k = [], None, 0
+    for i in range(total):
+        if fresh[i]:
+            stratum, k = mine[k], k + 1
+            obj = _object_for(family, rng, stratum)
+        else:
+            options = compatible(family, obj)
+            stratum = options[int(rng.integers(0, len(options)))]
+        c = {"family": family, "seed": seed, "case": i, "reuse": not fresh[i], "object": obj}
+        c.update(_draw_call(family, rng, stratum, obj, edges.get(i)))
+        assert stratum_of(c) == stratum, (c, stratum)
+        cases.append(c)
+    return cases
+
+
+def stratum_of(c):
+    """The kernel instantiation a case launches, from the arguments of its call alone."""
+    f = c["family"]
+    if f in ("rbk", "sbk"):
+        ks = _size(TR._NP[c["kt"]])
+        if f == "rbk" and not c["want_a"]:
+            kind = "keys_only"
+        elif c["vt"] is None:
+            kind = "len_" + c["st"]
+        else:
+            kind = (c["vt"], c["st"], c["op"])
+        return (ks, kind) if f == "rbk" else (ks, kind, c["inclusive"])
+    if f == "hist":
+        info = np.iinfo(TH._NP[c["kt"]])
+        copies, L = hist_limits(_size(TH._NP[c["st"]]))
+        cvt = "cnt_" + c["st"] if c["vt"] is None else "%s->%s" % (c["vt"], c["st"])
+        return (info.bits // 8, int(info.min < 0), cvt, "copies" if c["num_bins"] <= copies else "peel" if c["num_bins"] <= L else "global")
+    return (c["kt"], c["mode"])
+
+
+def by_key_inputs(c):
+    """(keys, values) of a reduce-by-key or scan-by-key case."""
+    n, tile, s = c["n"], c["tile"], c["structure"]
+    if s["kind"] == "unsorted":
+        runs = TR.structure("unsorted", n, tile, seed=s["seed"])
+    else:
+        parts, base = [], 0
+        bounds = [0] + list(s["cuts"]) + [n]
+        for k, mean in enumerate(s["means"]):
+            r = TR.structure("geo%d" % mean, bounds[k + 1] - bounds[k], tile, seed=s["seed"] + k)
+            parts.append(r + base)
+            base += int(r[-1]) + 1 if r.size else 0
+        runs = np.concatenate(parts).astype(np.int64)
+    if s["long"]:
+        at, ln = s["long"]
+        runs[at:at + ln] = runs[at]
+    return TR.make_keys(c["kt"], runs, seed=c["palette_seed"]), TR.make_values(c["vt"], n, c["value_seed"])
+
+
+def longest_run(keys):
+    if not keys.size:
+        return 0
+    return int(np.diff(np.append(np.flatnonzero(sbk_model.heads_of(keys)), keys.size)).max())
+
+
+def hist_inputs(c):
+    """(keys, values, prior content of hist_out) of a histogram case."""
+    kt, n, lower, shift, nb = c["kt"], c["n"], c["lower"], c["shift"], c["num_bins"]
+    rng = np.random.default_rng(c["data_seed"])
+    bits = lambda m: rng.integers(0, 1 << 63, m, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, m, dtype=np.uint64)
+    if c["layout"] == "handful":
+        few = rng.integers(0, TH.span_of(kt, lower, shift, nb), 5, dtype=np.uint64)
+        near = TH.key_at(kt, lower, few[rng.integers(0, 5, n)])
+    else:
+        near = TH.make_keys(kt, c["layout"], n, lower, shift, nb, seed=c["data_seed"])
+    anywhere = bits(n).astype(TH._UBITS[near.itemsize]).view(near.dtype)
+    keys = np.where(rng.random(n) < c["outside"], anywhere, near)
+    sdt = np.dtype(TH._NP[c["st"]])
+    return keys, TH.make_values(c["vt"], n, c["data_seed"]), bits(nb).astype(TH._UBITS[sdt.itemsize]).view(sdt)
+
+
+def merge_inputs(c):
+    """(keys_a, keys_b) of a merge case, both in the merge's order."""
+    kt, na, nb, seed = c["kt"], c["na"], c["nb"], c["data_seed"]
+    if c["ranges"] == "overlapping":
+        return TM.keys_of_type(kt, na, seed), TM.keys_of_type(kt, nb, seed + 1)
+    both = TM.keys_of_type(kt, na + nb, seed)
+    if c["ranges"] == "a_below_b":
+        return both[:na], both[na:]
+    if c["ranges"] == "b_below_a":
+        return both[nb:], both[:nb]
+    to_a = np.zeros(na + nb, bool)
+    to_a[np.random.default_rng(seed).permutation(na + nb)[:na]] = True
+    return both[to_a], both[~to_a]
+
+
+def _make_object(clo, ctx, family, obj):
+    if family == "rbk":
+        return clo.ReduceByKey(ctx, obj[0], obj[1], obj[2], op=obj[3])
+    if family == "sbk":
+        return clo.ScanByKey(ctx, obj[0], obj[1], obj[2], op=obj[3], inclusive=obj[4])
+    if family == "hist":
+        return clo.Histogram(ctx, obj[0], obj[1], obj[2], options="accumulate" if obj[3] else None)
+    return clo.Merge(ctx, obj[0], obj[1])
+
+
+def _run_one(dev, c, handle):
+    """The family's own run_case / run_merge: outputs equal the model, rows beyond m untouched, guards intact, inputs
+    unchanged, the run count exact."""
+    f, what = c["family"], "%s seed %d case %d" % (c["family"], c["seed"], c["case"])
+    if f == "rbk":
+        keys, values = by_key_inputs(c)
+        TR.run_case(dev, c["kt"], c["vt"], c["st"], c["op"], keys, values, what, offs=tuple(c["offs"]), want_k=c["want_k"], want_a=c["want_a"], obj=handle)
+    elif f == "sbk":
+        keys, values = by_key_inputs(c)
+        TS.run_case(dev, c["kt"], c["vt"], c["st"], c["op"], c["inclusive"], keys, values, what, offs=tuple(c["offs"]), in_place=c["in_place"], obj=handle)
+    elif f == "hist":
+        keys, values, prior = hist_inputs(c)
+        assert handle.accumulate == c["accumulate"]
+        TH.run_case(dev, c["kt"], c["vt"], c["st"], keys, values, c["lower"], c["shift"], c["num_bins"], what, offs=tuple(c["offs"]), obj=handle, prefill=prior)
+    else:
+        a, b = merge_inputs(c)
+        TM.run_merge(dev, c["kt"], a, b, c["mode"], what, offs=tuple(c["offs"]), obj=handle)
+
+
+def _fuzz_family(gpu, family, seed):
+    import cl_ops_amd as clo
+    ctx, q = gpu
+    dev = (clo, ctx, q)
+    handle = None
+    try:
+        for c in draw_cases(family, seed):
+            try:
+                if not c["reuse"]:
+                    if handle is not None:
+                        handle.close()
+                    handle = _make_object(clo, ctx, family, c["object"])
+                _run_one(dev, c, handle)
+            except Exception as e:  # noqa: BLE001 (the description makes the failure reproducible from the message alone)
+                raise AssertionError("fuzz %s seed %d case %d: %s: %s\n%r" % (family, seed, c["case"], type(e).__name__, e, c)) from e
+    finally:
+        if handle is not None:
+            handle.close()
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["rbk"]))
+def test_fuzz_reduce_by_key(gpu, seed):
+    _fuzz_family(gpu, "rbk", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["sbk"]))
+def test_fuzz_scan_by_key(gpu, seed):
+    _fuzz_family(gpu, "sbk", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["hist"]))
+def test_fuzz_histogram(gpu, seed):
+    _fuzz_family(gpu, "hist", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["merge"]))
+def test_fuzz_merge(gpu, seed):
+    _fuzz_family(gpu, "merge", seed)

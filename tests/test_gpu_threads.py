@@ -1,7 +1,10 @@
 """Distinct sorter / scanner objects used from distinct host threads at the same time, each on its own queue, one shared
 context: the threading contract of the reference (no locks, no mutable globals: an object is not re-entrant, distinct
 objects are independent — SURVEY §8b "Threading"). ctypes drops the GIL during a call, so the C drivers, their workspace
-caches and the run-time compiler really do run side by side here. Every result is checked bit for bit against numpy."""
+caches and the run-time compiler really do run side by side here. Every result is checked bit for bit against numpy.
+The by-key sort, reduce by key, scan by key, histogram and merge run the same way (the adapters of
+test_gpu_by_key_queues.py: inputs, the device call, the host-data call and the model of each), and give their device
+memory back like the sorters and scanners."""
 import threading
 
 import numpy as np
@@ -79,6 +82,53 @@ def test_distinct_objects_on_distinct_threads(clo):
         threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "uint", 16, 30, 23, errors)),
         threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "ulong", 17, 30, 22, errors)),
     ]
+    for w in workers:
+        w.start()
+    for w in workers:
+        w.join(timeout=600)
+    assert not any(w.is_alive() for w in workers), "a worker is stuck"
+    assert errors == []
+    ctx.close()
+
+
+def _by_key_worker(clo, ctx, kind, seed, rounds, max_log2, errors):
+    """One object of one of the five by-key kinds on a queue of its own: random sizes, device data."""
+    name = kind.__name__.strip("_")
+    try:
+        rng = np.random.default_rng(seed)
+        k = kind()
+        q = clo.Queue(ctx)
+        obj = k.new(clo, ctx)
+        for _ in range(rounds):
+            n = int(rng.integers(1, 1 << int(rng.integers(4, max_log2 + 1))))
+            ins = k.inputs(n, int(rng.integers(0, 1 << 30)))
+            want = k.want(ins)
+            dev_in = [clo.Buffer(ctx, max(a.nbytes, 16)) for a in ins]
+            for b, a in zip(dev_in, ins):
+                b.write(q, a)
+            dev_out = [clo.Buffer(ctx, max(cnt * np.dtype(t).itemsize, 16)) for cnt, t in zip(k.out_counts(ins), k.out_types)]
+            k.call(obj, q, dev_in, dev_out, ins)
+            got = [b.read(q, t, w.size) for b, t, w in zip(dev_out, k.out_types, want)]
+            if not all(np.array_equal(g, w) for g, w in zip(got, want)):
+                errors.append("%s n=%d: wrong result" % (name, n))
+            for b in dev_in + dev_out:
+                b.close()
+        obj.close()
+        q.close()
+    except Exception as e:  # noqa: BLE001
+        errors.append("%s: %r" % (name, e))
+
+
+def test_by_key_objects_on_distinct_threads(clo):
+    """Seven threads in one process: the five by-key kinds next to one satradix sorter and one scanner."""
+    import test_gpu_by_key_queues as K
+    ctx = clo.Context(0)
+    errors = []
+    workers = [threading.Thread(target=_by_key_worker, args=(clo, ctx, kind, 40 + i, 16, 21, errors))
+               for i, kind in enumerate((K._SortByKey, K._ReduceByKey, K._ScanByKey, K._Histogram, K._Merge))]
+    workers += [threading.Thread(target=_sort_worker, args=(clo, ctx, "satradix", "uint", 46, 16, 21, errors)),
+                threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "ulong", 47, 16, 21, errors))]
+    assert len(workers) == 7
     for w in workers:
         w.start()
     for w in workers:
@@ -199,6 +249,48 @@ def test_objects_give_their_device_memory_back(clo):
         got = sc.with_host_data(b, q)
         assert int(got[-1]) == int(b[:-1].sum())
         sc.close()
+        q.close()
+
+    cycle()                       # (first use: code objects, the runtime's own pools)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(12):
+        cycle()
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    assert free0 - free1 < (64 << 20), "device memory lost over 12 cycles: %.1f MiB" % ((free0 - free1) / 2**20)
+    ctx.close()
+
+
+def test_by_key_objects_give_their_device_memory_back(clo):
+    """The same for a by-key sorter (two numel x 8-byte pair buffers cached per sorter), a reduce by key, a scan by key, a
+    histogram and a merge (a cached workspace each): created, used at 2^21 elements through the device and the host-data
+    form, and destroyed, over and over."""
+    import torch
+    import test_gpu_by_key_queues as K
+    ctx = clo.Context(0)
+    n = 1 << 21
+    kinds = [kind() for kind in (K._SortByKey, K._ReduceByKey, K._ScanByKey, K._Histogram, K._Merge)]
+    data = []
+    for i, k in enumerate(kinds):
+        ins = k.inputs(n, 60 + i)
+        data.append((k, ins, k.want(ins)))
+
+    def cycle():
+        q = clo.Queue(ctx)
+        for k, ins, want in data:
+            obj = k.new(clo, ctx)
+            dev_in = [clo.Buffer(ctx, a.nbytes) for a in ins]
+            for b, a in zip(dev_in, ins):
+                b.write(q, a)
+            dev_out = [clo.Buffer(ctx, max(cnt * np.dtype(t).itemsize, 16)) for cnt, t in zip(k.out_counts(ins), k.out_types)]
+            k.call(obj, q, dev_in, dev_out, ins)
+            for b, t, w in zip(dev_out, k.out_types, want):
+                assert np.array_equal(b.read(q, t, w.size), w)
+            for g, w in zip(k.host(obj, q, ins), want):
+                assert np.array_equal(g, w)
+            for x in dev_in + dev_out + [obj]:
+                x.close()
         q.close()
 
     cycle()                       # (first use: code objects, the runtime's own pools)
