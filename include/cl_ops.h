@@ -14,6 +14,7 @@
 #include "clo_scan_by_key.h"
 #include "clo_histogram.h"
 #include "clo_merge.h"
+#include "clo_search.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

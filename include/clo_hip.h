@@ -252,6 +252,37 @@ int clo_hip_merge(const void* keys_a, const void* values_a, size_t numel_a,
 	void* keys_out, void* values_out, int key_size, int key_kind,
 	int value_size, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- search (new functionality: CloSearch, include/clo_search.h) ----
+ * pos_out[i], a uint, = how many of haystack[0, numel_h), ascending, are < needles[i] (flags & CLO_HIP_SEARCH_UPPER:
+ * <= needles[i]), for i in [0, numel_n). Keys are key_size (1, 2, 4, 8) bytes and compare by key_kind as in
+ * clo_hip_merge. CLO_HIP_SEARCH_NEEDLES_SORTED: the caller promises that the needles are ascending too; the results
+ * are then the same and each touched haystack key is read once (two launches: the tiles' ranges of the haystack into
+ * the workspace, then one work-group per tile of needles). Without it: one launch of a grid-stride loop over the
+ * tiles, at most max_groups work-groups when max_groups is not 0 (tests walk the loop with 1, 2, 3); max_groups bounds
+ * the second launch of the sorted form too.
+ * CLO_HIP_EARGS before anything is enqueued: key_kind out of range, other flag bits, numel_h or numel_n >= 2^32, NULL
+ * haystack with numel_h > 0, NULL needles or pos_out with numel_n > 0, a pointer not aligned to its element, a
+ * missing or misaligned workspace where clo_hip_search_workspace_bytes is not 0. Sizes not built:
+ * CLO_HIP_EUNSUPPORTED. A workspace below that size: CLO_HIP_EWORKSPACE. pos_out must not overlap an input (not
+ * checked here: the driver does). numel_n 0 launches nothing; numel_h 0 writes zeros and reads no haystack. On a
+ * haystack that is not sorted, or needles that break the promise, the contents of pos_out are unspecified; reads stay
+ * inside the inputs, writes inside pos_out[0, numel_n), every value written is <= numel_h. No work-group waits for
+ * another; asynchronous on `stream`; nothing is allocated and the host never waits, so the call can be captured into
+ * a graph.
+ * clo_hip_search_tile: needles per tile; clo_hip_search_lds_keys: the longest haystack (general form) or range of it
+ * (sorted form) a work-group keeps in LDS; clo_hip_search_pivots: the entries of the sampled table the general form
+ * keeps in LDS for a longer haystack; each 0 for key sizes not built. clo_hip_search_workspace_bytes is monotone in
+ * numel_n, 0 for numel_n = 0, for numel_h = 0 and without CLO_HIP_SEARCH_NEEDLES_SORTED. */
+#define CLO_HIP_SEARCH_UPPER          1u
+#define CLO_HIP_SEARCH_NEEDLES_SORTED 2u
+size_t clo_hip_search_tile(int key_size);
+size_t clo_hip_search_lds_keys(int key_size);
+size_t clo_hip_search_pivots(int key_size);
+size_t clo_hip_search_workspace_bytes(size_t numel_h, size_t numel_n, unsigned flags);
+int clo_hip_search(const void* haystack, size_t numel_h, const void* needles, size_t numel_n, void* pos_out,
+	int key_size, int key_kind, unsigned flags, unsigned max_groups,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
