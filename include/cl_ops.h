@@ -15,6 +15,7 @@
 #include "clo_histogram.h"
 #include "clo_merge.h"
 #include "clo_search.h"
+#include "clo_setop.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

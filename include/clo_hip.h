@@ -283,6 +283,35 @@ int clo_hip_search(const void* haystack, size_t numel_h, const void* needles, si
 	int key_size, int key_kind, unsigned flags, unsigned max_groups,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- set operations (new functionality: CloSetOp, include/clo_setop.h) ----
+ * The multiset union, intersection, difference (A - B) or symmetric difference of keys_a[0, numel_a) and keys_b[0,
+ * numel_b), each ascending: the subsequence of clo_hip_merge's output that the op keeps (include/clo_setop.h has the
+ * table), written to keys_out[0, k) and values_out[0, k); *num_out = k, a uint64_t of device memory, 8-byte aligned.
+ * Nothing is written at index >= k. The outputs hold at least the op's capacity: numel_a + numel_b (union, symmetric
+ * difference), min(numel_a, numel_b) (intersection), numel_a (difference). Keys, key_kind, value_size and the arg form
+ * (value_size 4 and NULL values: the element's index in A || B) are clo_hip_merge's. Intersection and difference keep
+ * no element of B: values_b is not looked at.
+ * CLO_HIP_EARGS before anything is enqueued: clo_hip_merge's list, an op outside the four, num_out NULL or not 8-byte
+ * aligned. CLO_HIP_EUNSUPPORTED and CLO_HIP_EWORKSPACE as clo_hip_merge. No output may overlap an input, the other
+ * output or num_out (not checked here: the driver does). n 0 needs no workspace and still writes *num_out = 0. On
+ * inputs that are not sorted k and the contents are unspecified; reads stay inside the inputs, writes inside [0,
+ * capacity) of the outputs, k <= capacity.
+ * Four launches (the tiles' split points, the tiles' kept counts, one work-group that turns the counts into offsets
+ * and writes num_out, the compacting merge); no work-group waits for another and there are no atomics; asynchronous on
+ * `stream`; nothing is allocated and the host never waits, so the call can be captured into a graph.
+ * clo_hip_setop_tile: the merged elements per tile, 0 for sizes not built. clo_hip_setop_workspace_bytes is monotone
+ * in numel_a + numel_b and 0 for n = 0. */
+#define CLO_HIP_SETOP_UNION                0
+#define CLO_HIP_SETOP_INTERSECTION         1
+#define CLO_HIP_SETOP_DIFFERENCE           2
+#define CLO_HIP_SETOP_SYMMETRIC_DIFFERENCE 3
+size_t clo_hip_setop_tile(int key_size, int value_size);
+size_t clo_hip_setop_workspace_bytes(size_t numel_a, size_t numel_b);
+int clo_hip_setop(int op, const void* keys_a, const void* values_a, size_t numel_a,
+	const void* keys_b, const void* values_b, size_t numel_b,
+	void* keys_out, void* values_out, uint64_t* num_out, int key_size, int key_kind,
+	int value_size, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----

@@ -31,7 +31,8 @@
  * writes).
  *
  * Out of scope: descending order, a key field inside a wider element (get_key), run-time compiled
- * comparisons, more than two inputs, set operations (union, intersection, difference).
+ * comparisons, more than two inputs. The set operations on sorted arrays (union, intersection, difference, symmetric
+ * difference) are CloSetOp, include/clo_setop.h.
  */
 #ifndef CLO_MERGE_H
 #define CLO_MERGE_H
