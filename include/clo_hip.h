@@ -312,6 +312,44 @@ int clo_hip_setop(int op, const void* keys_a, const void* values_a, size_t numel
 	void* keys_out, void* values_out, uint64_t* num_out, int key_size, int key_kind,
 	int value_size, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- selection and partition (new functionality: CloSelect, include/clo_select.h) ----
+ * Element i of keys_in[0, numel) is KEPT iff flags[i] != 0 (pred CLO_HIP_SELECT_FLAGGED: flags_or_threshold points to
+ * numel bytes, the keys are opaque) or iff keys_in[i] <pred> threshold in clo_hip_merge's order of key_kind (0 unsigned,
+ * 1 signed, 2 IEEE total order; flags_or_threshold points to ONE key in device memory, aligned to key_size). The order
+ * is total: EQ means equal bits. op CLO_HIP_SELECT_SELECT: the k kept elements go to rows [0, k) of keys_out and
+ * values_out in input order, rows >= k are not written. CLO_HIP_SELECT_PARTITION: the rejected elements go to rows [k,
+ * numel) behind them, in input order too. *num_out = k, a uint64_t of device memory, 8-byte aligned. The outputs hold
+ * numel rows. value_size 0 (none), 4 or 8: opaque words; value_size 4 with values_in NULL: values_out[j] is the
+ * element's index (the arg form); keys_out may then be NULL, and with FLAGGED keys_in too.
+ * CLO_HIP_EARGS before anything is enqueued: an op, pred or key_kind out of range, numel >= 2^32, flags_or_threshold
+ * NULL (but the flags of numel 0), num_out NULL or not 8-byte aligned, both outputs NULL, values (in or out) with value_size 0, values_out NULL
+ * with value_size > 0, NULL values_in with value_size 8, keys_in NULL with numel > 0 where the keys are read (a comparison, or
+ * keys_out given), a pointer not aligned to its element, a missing or misaligned workspace with numel > 0. Sizes not
+ * built: CLO_HIP_EUNSUPPORTED. A workspace below clo_hip_select_workspace_bytes(numel, key_size, value_size):
+ * CLO_HIP_EWORKSPACE. No output may overlap an input, the flags, the threshold, the other output or num_out (not
+ * checked here: the driver does). numel 0 needs no workspace and still writes *num_out = 0.
+ * Whatever the arrays hold, reads stay inside the inputs, writes inside [0, numel) of the outputs, and k <= numel.
+ * Three launches (the tiles' kept counts; one work-group that turns them into offsets and writes num_out, taking
+ * CLO_HIP_SELECT_SCAN_TRIP counts per trip of its loop; the compacting sweep); no work-group waits for another and there
+ * are no atomics; asynchronous on `stream`; nothing is allocated and the host never waits, so the call can be captured
+ * into a graph. clo_hip_select_tile: the elements per tile, 0 for sizes not built. clo_hip_select_workspace_bytes is
+ * monotone in numel, 0 for numel 0 and a multiple of CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_SELECT_SELECT    0
+#define CLO_HIP_SELECT_PARTITION 1
+#define CLO_HIP_SELECT_FLAGGED 0
+#define CLO_HIP_SELECT_LT      1
+#define CLO_HIP_SELECT_LE      2
+#define CLO_HIP_SELECT_GT      3
+#define CLO_HIP_SELECT_GE      4
+#define CLO_HIP_SELECT_EQ      5
+#define CLO_HIP_SELECT_NE      6
+#define CLO_HIP_SELECT_SCAN_TRIP 2048
+size_t clo_hip_select_tile(int key_size, int value_size);
+size_t clo_hip_select_workspace_bytes(size_t numel, int key_size, int value_size);
+int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in, const void* flags_or_threshold,
+	void* keys_out, void* values_out, uint64_t* num_out, size_t numel, int key_size, int key_kind,
+	int value_size, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
