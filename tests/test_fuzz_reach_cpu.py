@@ -2,15 +2,22 @@
 stratum of every family's table (every kernel instantiation) is drawn, the random parts cover what they promise (sizes
 0, 1, tile +- 1 and non-multiples of the tile, a run longer than two tiles, objects reused for a larger and a smaller
 call, views off their alignment, the wrap trap), and the vectorised models agree with plain Python loops on the
-generator's own odd inputs (NaN payloads, unsorted keys, wrapping sums)."""
+generator's own odd inputs (NaN payloads, unsorted keys, wrapping sums). For search, the set operations and select:
+every haystack, needle, range, run and threshold kind is seen, every (key type, pred), (op, pred) and (op, form) of
+select is drawn, the inputs are in the library's order wherever the case promises it, and search_model, setop_model
+and select_model equal element-by-element loops written from the headers' definitions."""
 import numpy as np
 import pytest
 
 import test_gpu_fuzz as F
+from merge_model import order_key
 from rbk_model import rbk
 from sbk_model import sbk, sbk_loop, identity
+from search_model import search
+from select_model import select
+from setop_model import setop
 
-FAMILIES = ["rbk", "sbk", "hist", "merge"]
+FAMILIES = ["rbk", "sbk", "hist", "merge", "search", "setop", "select"]
 _ALL = {}
 
 
@@ -25,6 +32,9 @@ def test_the_tables_hold_every_instantiation():
     assert len(F.STRATA["sbk"]) == 4 * (2 + 4 * 3) * 2 == 112
     assert len(F.STRATA["hist"]) == 4 * 2 * 6 * 3 == 144
     assert len(F.STRATA["merge"]) == 11 * 5 == 55
+    assert len(F.STRATA["search"]) == 11 * 2 * 2 == 44
+    assert len(F.STRATA["setop"]) == 11 * 5 * 4 == 220
+    assert len(F.STRATA["select"]) == 11 * 5 * 2 + 11 == 121
     for f in FAMILIES:
         assert len(set(F.STRATA[f])) == len(F.STRATA[f])
         assert F.SEEDS[f] * F.CASES[f] >= 2 * len(F.STRATA[f])
@@ -54,7 +64,8 @@ def test_draw_cases_is_a_pure_function(family):
 @pytest.mark.parametrize("family", FAMILIES)
 def test_sizes_offsets_and_reuse(family):
     cases = cases_of(family)
-    sizes = [(n, c["tile"]) for c in cases for n in ((c["na"], c["nb"]) if family == "merge" else (c["n"],))]
+    two = {"merge": ("na", "nb"), "setop": ("na", "nb"), "search": ("nh", "nn")}.get(family, ("n",))
+    sizes = [(c[k], c["L"] if k == "nh" else c["tile"]) for c in cases for k in two]       # (the haystack's unit is L)
     for special in (lambda n, t: n == 0, lambda n, t: n == 1, lambda n, t: n == t - 1, lambda n, t: n == t + 1, lambda n, t: n == t,
                     lambda n, t: n > 4 * t, lambda n, t: n > 1 << 18):
         assert any(special(n, t) for n, t in sizes)
@@ -63,7 +74,7 @@ def test_sizes_offsets_and_reuse(family):
     offs = {o for c in cases for o in c["offs"]}
     assert all(0 <= o <= 31 for o in offs) and len(offs) > 16 and any(o % 2 for o in offs) and max(offs) >= 28
     # an object reused: about half of the cases, its constructor arguments unchanged, sizes up and down
-    total = lambda c: c["na"] + c["nb"] if family == "merge" else c["n"]
+    total = lambda c: sum(c[k] for k in two)
     reused = [(a, b) for a, b in zip(cases, cases[1:]) if b["reuse"]]
     assert len(cases) // 3 <= len(reused) <= 2 * len(cases) // 3
     assert all(a["object"] == b["object"] and a["seed"] == b["seed"] for a, b in reused)
@@ -149,7 +160,6 @@ def test_histogram_cases():
 
 
 def test_merge_cases():
-    from merge_model import order_key
     cases = cases_of("merge")
     assert {c["ranges"] for c in cases} == {"overlapping", "a_below_b", "b_below_a", "interleaved"}
     assert any(c["na"] == 0 for c in cases) and any(c["nb"] == 0 for c in cases) and all(c["na"] + c["nb"] for c in cases)
@@ -165,3 +175,206 @@ def test_merge_cases():
             assert order_key(a)[-1] <= order_key(b)[0]
         if c["ranges"] == "b_below_a" and a.size and b.size:
             assert order_key(b)[-1] <= order_key(a)[0]
+
+
+def in_order(x):
+    k = order_key(x)
+    return bool(np.all(k[:-1] <= k[1:]))
+
+
+def search_loop(hay, ndl, upper):
+    """clo_search.h: the number of haystack keys < the needle (upper: <= it), counted one by one."""
+    oh, on = [int(x) for x in order_key(hay)], [int(x) for x in order_key(ndl)]
+    return [sum(1 for h in oh if (h <= x if upper else h < x)) for x in on]
+
+
+def test_search_cases():
+    cases = cases_of("search")
+    seen, looped = set(), 0
+    for c in cases:
+        P, L = c["P"], c["L"]
+        seen.add(("nh", [e(P, L) for e in F._HAY_EDGES].index(c["nh"])) if c["nh"] in [e(P, L) for e in F._HAY_EDGES] else "nh off the edges")
+        if c["nh"] + c["nn"] > 40000:
+            continue
+        hay, ndl = F.search_inputs(c)
+        dt = np.dtype(F.TSE._NP[c["kt"]])
+        assert hay.size == c["nh"] and ndl.size == c["nn"] and hay.dtype == ndl.dtype == dt
+        assert in_order(hay) and (in_order(ndl) or not c["sorted"]), c
+        seen.update((("hay", c["hay"]), ("needles", c["needles"])))
+        oh, on = order_key(hay), order_key(ndl)
+        bits = lambda x: set(x.view("u%d" % dt.itemsize).tolist())
+        if c["hay"] == "equal" and c["nh"]:
+            assert len(bits(hay)) == 1
+        if c["hay"] == "tie_run":                                     # longer than L, and a pivot of the general path inside it
+            at, ln = c["tie"]
+            assert ln > L and len(bits(hay[at:at + ln])) == 1 and any(at <= k * c["nh"] // P < at + ln for k in range(1, P)), c
+        if c["needles"] == "hits" and c["nn"]:
+            assert bits(ndl) <= bits(hay)
+        if c["needles"] == "neighbours" and c["nn"]:
+            near = {(x + d) % (1 << (8 * dt.itemsize)) for x in oh.tolist() for d in (-1, 1)}
+            assert set(on.tolist()) <= near
+            if dt.kind == "f" and np.isnan(ndl).any() and not bits(ndl[np.isnan(ndl)]) <= bits(hay):
+                seen.add("a NaN payload next to a key")
+            zero = lambda x, neg: bool(((x == 0) & (np.signbit(x) == neg)).any())
+            if dt.kind == "f" and ((zero(ndl, True) and zero(hay, False)) or (zero(ndl, False) and zero(hay, True))):
+                seen.add("the other zero")                             # -0 and +0 are neighbours in the library's order
+        if c["needles"] == "below" and c["nn"] and on.max() < oh[0]:
+            seen.add("all below")
+        if c["needles"] == "above" and c["nn"] and on.min() > oh[-1]:
+            seen.add("all above")
+        if c["needles"] == "one_key" and c["nn"] > 50:
+            assert np.bincount(np.unique(on, return_inverse=True)[1]).max() > 0.8 * c["nn"]
+        if not c["nn"]:
+            seen.add("no needles")
+        if c["nh"] * c["nn"] <= 400000:
+            looped += 1
+            assert search(hay, ndl, c["upper"]).tolist() == search_loop(hay, ndl, c["upper"]), c
+    assert looped >= len(cases) // 6
+    want = {("hay", k) for k in F.HAY_KINDS} | {("needles", k) for k in F.NEEDLE_KINDS} | {("nh", i) for i in range(len(F._HAY_EDGES))}
+    assert seen >= want | {"nh off the edges", "a NaN payload next to a key", "the other zero", "all below", "all above", "no needles"}, want - seen
+    # a key type other than uint with the edges P and L, on both paths
+    for edge in (2, 3, 4, 5, 6, 7):
+        assert any(c["kt"] != "uint" and c["nh"] == F._HAY_EDGES[edge](c["P"], c["L"]) for c in cases), edge
+
+
+def setop_loop(op, a, b):
+    """clo_setop.h: x occurs m times in A and n times in B, A's element is the r-th of its run and B's the s-th; the
+    table says which are kept; the output is in merge order, equal keys of A before those of B."""
+    oa, ob = [int(x) for x in order_key(a)], [int(x) for x in order_key(b)]
+    rows = []
+    for src, mine, other in ((0, oa, ob), (1, ob, oa)):
+        copies, met = {}, {}
+        for y in other:
+            copies[y] = copies.get(y, 0) + 1
+        for i, x in enumerate(mine):
+            rank = met.get(x, 0)                                                # r, or s: the equal keys before this one
+            met[x] = rank + 1
+            there = copies.get(x, 0)                                            # n, or m
+            keep = {"union": src == 0 or rank >= there, "intersection": src == 0 and rank < there, "difference": src == 0 and rank >= there,
+                    "symmetric_difference": rank >= there}[op]
+            if keep:
+                rows.append((x, src, i))
+    rows.sort()
+    return [len(oa) * src + i for x, src, i in rows]
+
+
+def test_setop_cases():
+    cases = cases_of("setop")
+    assert {c["ranges"] for c in cases} == set(F.SETOP_RANGES) and {c["runs"] for c in cases} == set(F.SETOP_RUNS)
+    assert {c["long"][0] for c in cases if c["long"]} == {"a", "b", "both"} and any(c["long"] is None for c in cases)
+    assert any(c["na"] == 0 for c in cases) and any(c["nb"] == 0 for c in cases) and all(c["na"] + c["nb"] for c in cases)
+    for op in F.TSO.OPS:                                   # values_b given and left out, whether the op looks at it or not
+        assert {c["pass_vb"] for c in cases if c["op"] == op} == {False, True}
+    looped, seen = 0, set()
+    for c in cases:
+        if c["na"] + c["nb"] > 30000:
+            continue
+        a, b = F.setop_inputs(c)
+        assert a.size == c["na"] and b.size == c["nb"] and a.dtype == b.dtype == np.dtype(F.TM._NP[c["kt"]])
+        assert in_order(a) and in_order(b), c
+        oa, ob = order_key(a), order_key(b)
+        if c["ranges"] == "a_eq_b":
+            assert np.array_equal(oa, ob)
+        if c["ranges"] == "a_subset_b":                   # as multisets
+            ua, ca = np.unique(oa, return_counts=True)
+            ub, cb = np.unique(ob, return_counts=True)
+            assert set(ua.tolist()) <= set(ub.tolist()) and all(ca <= cb[np.searchsorted(ub, ua)])
+        if not c["long"] and a.size and b.size:
+            if c["ranges"] == "a_below_b":
+                assert oa[-1] <= ob[0]
+            if c["ranges"] == "b_below_a":
+                assert ob[-1] <= oa[0]
+        if c["long"]:
+            where, la, lb = c["long"]
+            longest = lambda o: int(np.unique(o, return_counts=True)[1].max()) if o.size else 0
+            if c["ranges"] in F.SETOP_RANGES[:4]:
+                assert longest(oa) >= la and longest(ob) >= lb and (la > 2 * c["tile"] or where == "b") and (lb > 2 * c["tile"] or where == "a"), c
+                if where == "both":
+                    x = np.unique(oa, return_counts=True)
+                    x = x[0][x[1].argmax()]
+                    if int((oa == x).sum()) != int((ob == x).sum()) > 2 * c["tile"]:
+                        seen.add("one key longer than two tiles in both, of different lengths")
+            else:
+                assert longest(ob) > 2 * c["tile"]
+            seen.add("long " + where)
+        if c["runs"] == "distinct" and a.dtype.itemsize >= 4 and a.size > 100 and not c["long"] and c["ranges"] == "overlapping":
+            assert np.unique(oa).size > 0.8 * a.size
+            seen.add("mostly distinct")
+        if c["runs"] == "short" and a.size > 100 and np.unique(oa).size < 0.8 * a.size:
+            seen.add("short runs")
+        if c["na"] + c["nb"] <= 5000:
+            looped += 1
+            wk, p = setop(c["op"], a, b)
+            assert p.tolist() == setop_loop(c["op"], a, b), c
+            assert np.array_equal(wk.view(np.uint8), np.concatenate((a, b))[p].view(np.uint8))
+            seen.add(c["op"])
+    assert looped >= len(cases) // 8
+    assert seen >= {"long a", "long b", "long both", "one key longer than two tiles in both, of different lengths", "mostly distinct", "short runs"} | set(F.TSO.OPS), seen
+
+
+def select_loop(op, pred, keys, fot):
+    """clo_select.h: kept iff the flag is not 0, or iff the key <pred> the threshold in the library's order."""
+    if pred == "flagged":
+        kept = [int(f) != 0 for f in np.asarray(fot).view(np.uint8)]
+    else:
+        t = int(order_key(np.array([fot], dtype=keys.dtype))[0])
+        kept = [{"lt": x < t, "le": x <= t, "gt": x > t, "ge": x >= t, "eq": x == t, "ne": x != t}[pred] for x in (int(x) for x in order_key(keys))]
+    rows = [i for i, k in enumerate(kept) if k]
+    return rows + ([i for i, k in enumerate(kept) if not k] if op == "partition" else []), len(rows)
+
+
+def test_select_cases():
+    cases = cases_of("select")
+    kts, preds, ops = F.TM.KEY_TYPES, F.TSL.PREDS, F.TSL.OPS
+    assert {(c["kt"], c["pred"]) for c in cases} == {(kt, pred) for kt in kts for pred in preds}                       # the 77
+    assert {(c["op"], c["pred"]) for c in cases} == {(op, pred) for op in ops for pred in preds}                       # the 14
+    assert {(c["op"], c["mode"]) for c in cases} == {(op, m) for op in ops for m in F.TSL.MODES + ("arg_no_keys",)}
+    assert all(c["pred"] == "flagged" for c in cases if c["mode"] == "arg_no_keys")
+    assert {c["pattern"] for c in cases} == set(F.TSL.PATTERNS) and {c["keys"] for c in cases} == set(F.SELECT_KEYS)
+    assert {c["threshold"] for c in cases if c["pred"] != "flagged"} == set(F.THRESHOLDS)
+    # a CloSelect really reused: the (op, pred) of the case before on the same object, at a size of its own
+    again = [(a, b) for a, b in zip(cases, cases[1:]) if b["reuse"] and (a["op"], a["pred"]) == (b["op"], b["pred"])]
+    assert len(again) >= 20 and any(b["n"] > 4 * a["n"] > 0 for a, b in again) and any(a["n"] > 4 * b["n"] > 0 for a, b in again)
+    flags, looped, seen = set(), 0, set()
+    for c in cases:
+        if c["n"] > 40000:
+            continue
+        keys, fot = F.select_inputs(c)
+        dt = np.dtype(F.TM._NP[c["kt"]])
+        assert keys.size == c["n"] and keys.dtype == dt
+        mask = F.TSL.mask_of(c["pattern"], c["n"], c["tile"], c["data_seed"])
+        p, k = select(c["op"], c["pred"], keys, fot)
+        if c["pred"] == "flagged":
+            assert fot.dtype == np.uint8 and fot.size == c["n"] and k == int(mask.sum())
+            flags.update(fot.tolist())
+        else:
+            u = "u%d" % dt.itemsize
+            thr = np.array([fot], dtype=dt).reshape(1)              # what run_select hands to the device: the same bits
+            assert fot.dtype == dt and thr.view(u)[0] == np.array(fot).reshape(1).view(u)[0]
+            t, ok = int(order_key(thr)[0]), order_key(keys)
+            top = (1 << (8 * dt.itemsize)) - 1
+            occurs = bool((ok == t).any())
+            if c["threshold"] == "present" and c["n"] > 200 and 50 < k < c["n"] - 50:
+                assert occurs, c
+            if c["threshold"] == "between" and c["n"] > 1:
+                assert not occurs
+                if ok.min() < t < ok.max():
+                    seen.add("between two keys that occur")
+            if c["threshold"] == "least":
+                assert t == 0
+                if dt.kind == "f":
+                    assert np.isnan(thr[0]) and np.signbit(thr[0]) and thr.view(u)[0] == top                        # -NaN, the largest payload
+                seen.add("least, " + ("among the keys" if occurs else "below every key"))
+            if c["threshold"] == "greatest":
+                assert t == top
+                seen.add("greatest, " + ("among the keys" if occurs else "above every key"))
+            if k == int(mask.sum()) and 0 < k < c["n"]:
+                seen.add("the pattern kept by a comparison")
+        if c["n"] <= 5000:
+            looped += 1
+            lp, lk = select_loop(c["op"], c["pred"], keys, fot)
+            assert k == lk and p.tolist() == lp, c
+    assert flags == set(range(256))                        # flags take every byte value
+    assert looped >= len(cases) // 6
+    assert seen >= {"between two keys that occur", "least, among the keys", "least, below every key", "greatest, among the keys", "greatest, above every key",
+                    "the pattern kept by a comparison"}, seen

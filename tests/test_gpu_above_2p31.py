@@ -1,8 +1,9 @@
-"""Element indices above 2^31 in reduce by key, scan by key, histogram, merge and the by-key sort: n = 2^31 + 2^20 + 5
-uchar keys, the smallest shape at which an element index needs bit 31 and, with 4-byte outputs, a byte offset passes
-2^32, while everything stays at a few GiB. The inputs are made and the results checked on the device with torch, in
-chunks, so that the host never holds them (the method of test_indices_above_2p31_satradix_and_scan); every expectation
-is closed-form or a torch.bincount, and exact."""
+"""Element indices above 2^31 in reduce by key, scan by key, histogram, merge, the by-key sort, search and the set
+operations: n = 2^31 + 2^20 + 5 uchar keys, the smallest shape at which an element index (a position in the haystack, an
+index into A || B) needs bit 31 and, with 4-byte outputs, a byte offset passes 2^32, while everything stays at a few
+GiB. The inputs are made and the results checked on the device with torch, in chunks, so that the host never holds them
+(the method of test_indices_above_2p31_satradix_and_scan); every expectation is closed-form or a torch.bincount, and
+exact. (Select has its case in test_gpu_select.py.)"""
 import numpy as np
 import pytest
 
@@ -198,3 +199,125 @@ def test_argsort_by_key_with_keys_out(dev):
     assert bool((after == before).all())
     for x in bufs + [s]:
         x.close()
+
+
+def same(x, y):
+    """x == y everywhere. A helper, so that a failing assert does not print the operands: pytest's report of a failing
+    `==` walks both sides element by element, which on two device tensors of 2^28 elements never ends."""
+    return bool((x == y).all())
+
+
+def ascending(x):
+    return bool((x[1:] >= x[:-1]).all())
+
+
+def ramp(torch, n, z=0):
+    """x[i] = i * 256 // n as uchar, and the 257 starts of its values: start[k] is the first i with x[i] >= k. z > 0:
+    z zeros first and the values 1 .. 255 over the rest, x[i] = 1 + (i - z) * 255 // (n - z)."""
+    x = torch.empty(n, dtype=torch.uint8, device="cuda")
+    for lo, hi in chunks(n):
+        i = torch.arange(lo, hi, dtype=torch.int64, device="cuda")
+        x[lo:hi] = ((i * 256).div(n, rounding_mode="floor") if not z else torch.where(i < z, 0, 1 + ((i - z) * 255).div(n - z, rounding_mode="floor"))).to(torch.uint8)
+    if not z:
+        return x, [-(-k * n // 256) for k in range(257)]
+    return x, [0] + [z + -(-(k - 1) * (n - z) // 255) for k in range(1, 257)]
+
+
+@pytest.mark.parametrize("hay", ["ramp", "zeros up to 2^31 - 3, then the ramp"])
+@pytest.mark.parametrize("path", ["general", "sorted"])
+def test_search_positions(dev, path, hay):
+    """A haystack of N keys h[i] = i * 256 // N; the needles are every byte value, repeated to 3 tiles + 1 entries,
+    ascending under NEEDLES_SORTED and in a fixed permutation without. The lower bound of value k is start[k], the upper
+    bound start[k + 1]. Every search probes indices above 2^31 on its way, but with this haystack N itself (the upper
+    bound of 255) is the one position above 2^31, so the second haystack holds 2^31 - 3 zeros and spreads the values
+    1 .. 255 over the 2^20 + 8 keys behind them: all but the lower bounds of 0 and 1 need bit 31 or lie just below it.
+    pos_out has a canary behind it."""
+    clo, ctx, q, torch = dev
+    nn = 3 * clo.search_tile(1) + 1
+    z = 0 if hay == "ramp" else (1 << 31) - 3
+    hay, start = ramp(torch, N, z)
+    start = np.array(start, dtype=np.int64)
+    assert start[0] == 0 and start[256] == N and (np.diff(start) > 0).all()
+    ndl = np.sort(np.resize(np.arange(256, dtype=np.uint8), nn))
+    if path == "general":
+        ndl = ndl[np.random.default_rng(31).permutation(nn)]
+    needles = torch.from_numpy(ndl).cuda()
+    pos = torch.full((nn + 64,), CANARY * 0x01010101 - (1 << 32), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    bufs = [as_buffer(clo, ctx, hay), as_buffer(clo, ctx, needles), clo.Buffer(ctx, 4 * nn, device_ptr=pos.data_ptr())]
+    s = clo.Search(ctx, "uchar")
+    try:
+        for upper in (False, True):
+            pos.fill_(CANARY * 0x01010101 - (1 << 32))
+            torch.cuda.synchronize()
+            assert s.with_device_data(q, bufs[0], N, bufs[1], nn, bufs[2], upper=upper, needles_sorted=path == "sorted")
+            q.finish()
+            got = pos.cpu().numpy().view(np.uint32)
+            want = start[ndl.astype(np.int64) + (1 if upper else 0)]
+            assert (want >= 1 << 31).sum() >= (nn // 2 if z else int(upper))
+            assert np.array_equal(got[:nn].astype(np.int64), want), "%s, %s" % (path, "upper" if upper else "lower")
+            assert (got[nn:] == CANARY * 0x01010101).all(), "pos_out was written behind its end"
+        assert np.array_equal(needles.cpu().numpy(), ndl), "the needles changed"
+        assert same(hay, ramp(torch, N, z)[0]), "the haystack changed"
+    finally:
+        for x in bufs + [s]:
+            x.close()
+        del hay, pos
+
+
+def _setop_case(dev, op, na, nb, rows_of, count_of):
+    """The arg form with keys_out of a[i] = i * 256 // na and b[i] = i * 256 // nb. count_of(ca, cb): the elements kept
+    of every value; rows_of(t, k, sa, sb, ca, cb): the index in A || B that row t of value k's stretch holds."""
+    clo, ctx, q, torch = dev
+    a, start_a = ramp(torch, na)
+    b, start_b = ramp(torch, nb)
+    T = lambda x: torch.tensor(x, dtype=torch.int64, device="cuda")
+    sa, sb = T(start_a[:256]), T(start_b[:256])
+    ca, cb = T(np.diff(start_a).tolist()), T(np.diff(start_b).tolist())
+    kept = count_of(ca, cb)
+    assert int(kept.min()) > 0
+    off = torch.cumsum(kept, 0) - kept                         # where value k's stretch starts in the output
+    total = int(kept.sum())
+    s = clo.SetOp(op, ctx, "uchar", 4)
+    cap = s.max_numel_out(na, nb)
+    assert (1 << 30) < total <= cap and 4 * total > 1 << 32     # values_out passes byte offset 2^32
+    ko = torch.full((cap,), CANARY, dtype=torch.uint8, device="cuda")
+    vo = torch.full((cap,), CANARY * 0x01010101 - (1 << 32), dtype=torch.int32, device="cuda")
+    cnt = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    bufs = [as_buffer(clo, ctx, t) for t in (a, b, ko, vo, cnt)]
+    try:
+        assert s.with_device_data(q, bufs[0], None, na, bufs[1], None, nb, bufs[2], bufs[3], bufs[4])
+        q.finish()
+        assert int(cnt[0]) == total
+        counts = torch.zeros(256, dtype=torch.int64, device="cuda")
+        above = 0
+        for lo, hi in chunks(total):
+            k = ko[lo:hi].to(torch.int64)
+            counts += torch.bincount(k, minlength=256)
+            assert ascending(k) and (lo == 0 or int(ko[lo - 1]) <= int(k[0])), "keys_out decreases in %d .. %d" % (lo, hi)
+            t = torch.arange(lo, hi, dtype=torch.int64, device="cuda") - off[k]
+            want = rows_of(t, k, sa, sb, ca, cb)
+            above += int((want > 1 << 31).sum())
+            assert same(vo[lo:hi].to(torch.int64) & 0xFFFFFFFF, want), "the indices, rows %d .. %d" % (lo, hi)
+        assert same(counts, kept) and above > 0
+        assert same(ko[total:], CANARY) and same(vo[total:], CANARY * 0x01010101 - (1 << 32)), "rows at index >= k were written"
+        assert same(a, ramp(torch, na)[0]) and same(b, ramp(torch, nb)[0]), "an input changed"
+    finally:
+        for x in bufs + [s]:
+            x.close()
+        del a, b, ko, vo
+
+
+def test_setop_difference_indices(dev):
+    """A - B with na = 2^31 + 5 and nb = 2^20: every value keeps its run of A without the first count_b[k] elements,
+    so k = na - nb, and the last rows hold indices above 2^31."""
+    _setop_case(dev, "difference", (1 << 31) + 5, 1 << 20, lambda t, k, sa, sb, ca, cb: sa[k] + cb[k] + t, lambda ca, cb: ca - cb)
+
+
+def test_setop_union_indices(dev):
+    """The roles swapped, na = 2^20 and nb = 2^31 + 5: every element of A is kept, then B's elements of rank >=
+    count_a[k] within their run, as na + j. The indices from B exceed 2^31 by more than na: the base of B's indices
+    (numel_a + the tile's first index of B - ..., mod 2^32) is what this is about."""
+    na = 1 << 20
+    _setop_case(dev, "union", na, (1 << 31) + 5, lambda t, k, sa, sb, ca, cb: (sa[k] + t).where(t < ca[k], na + sb[k] + t), lambda ca, cb: cb)

@@ -1,11 +1,11 @@
-"""The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram and CloMerge on the queue production uses (no
-profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace belongs to one
-queue at a time"): one object is called six times on two live queues in turn, with no host synchronisation between the
-calls and sizes that make it reuse and outgrow its workspace mid-sequence; then the queue of its last call is destroyed
-and the object is used on a third one, through the host-data and the device form. Last, the whole group-by pipeline
-(sort by key -> scan by key -> reduce by key -> histogram of the reduced keys -> merge of two such outputs) runs on one
-non-profiling queue without a finish() until the end, and gives the bits of the same pipeline on the session's
-profiling queue and of numpy. The results are compared, not the interleavings; everything is exact."""
+"""The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram, CloMerge, CloSearch, CloSetOp and CloSelect on the queue
+production uses (no profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace
+belongs to one queue at a time"): one object is called six times on two live queues in turn, with no host
+synchronisation between the calls and sizes that make it reuse and outgrow its workspace mid-sequence; then the queue of
+its last call is destroyed and the object is used on a third one, through the host-data and the device form. Last, the
+whole group-by pipeline (sort by key -> scan by key -> reduce by key -> histogram of the reduced keys -> merge of two
+such outputs) runs on one non-profiling queue without a finish() until the end, and gives the bits of the same pipeline
+on the session's profiling queue and of numpy. The results are compared, not the interleavings; everything is exact."""
 import numpy as np
 import pytest
 
@@ -13,6 +13,9 @@ from hist_model import histogram
 from merge_model import merge, order_key
 from rbk_model import rbk
 from sbk_model import sbk
+from search_model import search
+from select_model import select
+from setop_model import setop
 from test_gpu_reduce_by_key import structure, make_keys, make_values
 
 pytestmark = pytest.mark.gpu
@@ -144,6 +147,81 @@ class _Merge:
         return obj.with_host_data(ins[0], ins[2], ins[1], ins[3], q_exec=q)
 
 
+class _Search:
+    """n ushort haystack keys with many ties and about n / 4 ascending needles under NEEDLES_SORTED, the form whose
+    tiles' ranges live in the object's workspace. -> (pos_out,)."""
+    out_types = (np.uint32,)
+
+    def new(self, clo, ctx):
+        return clo.Search(ctx, "ushort")
+
+    def inputs(self, n, seed):
+        rng = np.random.default_rng(seed)
+        return np.sort(rng.integers(0, 5000, n).astype(np.uint16)), np.sort(rng.integers(0, 5100, max(1, n // 4)).astype(np.uint16))
+
+    def out_counts(self, ins):
+        return (ins[1].size,)
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], ins[0].size, i[1], ins[1].size, o[0], needles_sorted=True)
+
+    def want(self, ins):
+        return (search(ins[0], ins[1], False),)
+
+    def host(self, obj, q, ins):
+        return (obj.with_host_data(ins[0], ins[1], needles_sorted=True, q_exec=q),)
+
+
+class _SetOp(_Merge):
+    """The symmetric difference of _Merge's inputs. -> (the k keys, their values, k); the outputs hold the capacity."""
+    out_types = (np.uint16, np.uint32, np.uint64)
+
+    def new(self, clo, ctx):
+        return clo.SetOp("symmetric_difference", ctx, "ushort", 4)
+
+    def out_counts(self, ins):
+        return ins[0].size + ins[2].size, ins[0].size + ins[2].size, 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], i[1], ins[0].size, i[2], i[3], ins[2].size, o[0], o[1], o[2])
+
+    def want(self, ins):
+        wk, p = setop("symmetric_difference", ins[0], ins[2])
+        return wk, np.concatenate((ins[1], ins[3]))[p], np.array([p.size], np.uint64)
+
+    def host(self, obj, q, ins):
+        ko, vo = obj.with_host_data(ins[0], ins[2], ins[1], ins[3], q_exec=q)
+        return ko, vo, np.array([ko.size], np.uint64)
+
+
+class _Select:
+    """The partition of n uint keys by "lt" a threshold that lies in a one-element device buffer, uint values carried
+    along. -> (all n rows of keys and of values, the k kept ones first, and k)."""
+    out_types = (np.uint32, np.uint32, np.uint64)
+
+    def new(self, clo, ctx):
+        return clo.Select("partition", "lt", ctx, "uint", 4)
+
+    def inputs(self, n, seed):
+        rng = np.random.default_rng(seed)
+        return (rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32), rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32),
+                rng.integers(1 << 30, 3 << 30, 1, dtype=np.uint64).astype(np.uint32))
+
+    def out_counts(self, ins):
+        return ins[0].size, ins[0].size, 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], i[1], i[2], o[0], o[1], o[2], ins[0].size)
+
+    def want(self, ins):
+        p, k = select("partition", "lt", ins[0], ins[2][0])
+        return ins[0][p], ins[1][p], np.array([k], np.uint64)
+
+    def host(self, obj, q, ins):
+        ko, vo, k = obj.with_host_data(ins[0], ins[2][0], ins[1], q_exec=q)
+        return ko, vo, np.array([k], np.uint64)
+
+
 def _same(got, want, what):
     assert len(got) == len(want)
     for k, (g, w) in enumerate(zip(got, want)):
@@ -151,7 +229,7 @@ def _same(got, want, what):
             "%s: output %d differs from the model" % (what, k)
 
 
-@pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge], ids=lambda k: k.__name__.strip("_"))
+@pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge, _Search, _SetOp, _Select], ids=lambda k: k.__name__.strip("_"))
 def test_object_moves_between_queues(gpu, kind):
     import cl_ops_amd as clo
     ctx, _ = gpu

@@ -3,11 +3,12 @@ every path boundary (one-launch sorts, single-sweep passes, 8 192- and 16 384-el
 tiles), every radix, element types, in place / out of place, stable pairs — against
 numpy. Everything goes through the C-ABI of libcl_ops_hip.so.
 
-The second half is the STRATIFIED fuzz of reduce by key, scan by key, histogram and merge: the kernels of those four
-are templates over (key size x value -> sum conversion x op or mode), and draw_cases() walks the list of those
-instantiations, written out below from the public type rules, so that the committed seeds together launch every one;
-sizes, run structures, bounds, layouts, view offsets and the reuse of one object over a random sequence of sizes are
-random per case. draw_cases() and the *_inputs() functions touch no GPU: tests/test_fuzz_reach_cpu.py imports them."""
+The second half is the STRATIFIED fuzz of reduce by key, scan by key, histogram, merge, search, the set operations and
+select: the kernels of those seven are templates over (key size or type x value -> sum conversion, value form x op, mode
+or path), and draw_cases() walks the list of those instantiations, written out below from the public type rules, so that
+the committed seeds together launch every one; sizes, run structures, bounds, layouts, thresholds, view offsets and the
+reuse of one object over a random sequence of sizes are random per case. draw_cases() and the *_inputs() functions touch
+no GPU: tests/test_fuzz_reach_cpu.py imports them."""
 import math
 
 import numpy as np
@@ -19,6 +20,10 @@ import test_gpu_histogram as TH
 import test_gpu_merge as TM
 import test_gpu_reduce_by_key as TR
 import test_gpu_scan_by_key as TS
+import test_gpu_search as TSE
+import test_gpu_select as TSL
+import test_gpu_setop as TSO
+from merge_model import order_key, sort_keys
 
 pytestmark = pytest.mark.gpu
 
@@ -246,7 +251,7 @@ def test_fuzz_sharded_sort_loopback(gpu, seed):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# The stratified fuzz of the four by-key families
+# The stratified fuzz of the seven families
 # ----------------------------------------------------------------------------------------------------------------------
 
 _KT_BY_SIZE = {1: ["uchar"], 2: ["ushort"], 4: ["uint", "int", "float"], 8: ["ulong", "double"]}     # reduce / scan by key
@@ -257,20 +262,27 @@ _HIST_CVT = {"cnt_uint": (None, "uint"), "cnt_ulong": (None, "ulong"), "uint->ui
              "uint->ulong": ("uint", "ulong"), "long->long": ("long", "long")}
 _HIST_BINS = ["copies", "peel", "global"]      # <= the 32-copy limit | up to histogram_lds_bins | histogram_lds_bins + 1
 _MERGE_MODES = ["keys", "v4", "v8", "arg", "arg_only"]
+_SELECT_CMP = list(TSL.PREDS[1:])
 
 # Every kernel instantiation a family has, from the public type rules (include/clo_reduce.h, clo_scan_by_key.h,
-# clo_histogram.h, clo_merge.h; DESIGN.md for the three forms of the histogram), not from the kernels' enums.
+# clo_histogram.h, clo_merge.h, clo_search.h, clo_setop.h, clo_select.h; DESIGN.md for the three forms of the
+# histogram), not from the kernels' enums. search: (key type, upper, NEEDLES_SORTED); setop: (key type, value mode, op);
+# select: (key type, value form, by flags | by comparison), the indices of the set flags without keys_in being a form of
+# the flagged selection alone.
 STRATA = {
     "rbk": [(ks, kind) for ks in (1, 2, 4, 8) for kind in ["keys_only"] + _BK_KINDS],
     "sbk": [(ks, kind, incl) for ks in (1, 2, 4, 8) for kind in _BK_KINDS for incl in (False, True)],
     "hist": [(ks, sg, cvt, b) for ks in (1, 2, 4, 8) for sg in (0, 1) for cvt in _HIST_CVT for b in _HIST_BINS],
     "merge": [(kt, mode) for kt in TM.KEY_TYPES for mode in _MERGE_MODES],
+    "search": [(kt, upper, flag) for kt in TSE.KEY_TYPES for upper in (False, True) for flag in (False, True)],
+    "setop": [(kt, mode, op) for kt in TM.KEY_TYPES for mode in _MERGE_MODES for op in TSO.OPS],
+    "select": [(kt, mode, cls) for kt in TM.KEY_TYPES for mode in TSL.MODES for cls in ("flagged", "cmp")] + [(kt, "arg_no_keys", "flagged") for kt in TM.KEY_TYPES],
 }
 # seeds x cases >= 2 x strata: half the cases of a seed open a new stratum (with a new object), the other half reuse
 # the object of the case before them on a stratum it can run
-SEEDS = {"rbk": 2, "sbk": 3, "hist": 4, "merge": 2}
-CASES = {"rbk": 60, "sbk": 76, "hist": 72, "merge": 60}
-_SALT = {"rbk": 61, "sbk": 62, "hist": 63, "merge": 64}
+SEEDS = {"rbk": 2, "sbk": 3, "hist": 4, "merge": 2, "search": 2, "setop": 8, "select": 4}
+CASES = {"rbk": 60, "sbk": 76, "hist": 72, "merge": 60, "search": 60, "setop": 60, "select": 62}
+_SALT = {"rbk": 61, "sbk": 62, "hist": 63, "merge": 64, "search": 65, "setop": 66, "select": 67}
 
 
 def _size(x):
@@ -284,7 +296,11 @@ def _vsize(family, vt):
 def tile_of(family, ks, vs):
     """Elements per tile, from the library's getters (host code only)."""
     import cl_ops_amd as clo
-    t = {"rbk": clo.reduce_by_key_tile, "sbk": clo.scan_by_key_tile, "hist": clo.histogram_tile, "merge": clo.merge_tile}[family](ks, vs)
+    if family == "search":
+        t = clo.search_tile(ks)                       # needles per tile
+    else:
+        t = {"rbk": clo.reduce_by_key_tile, "sbk": clo.scan_by_key_tile, "hist": clo.histogram_tile, "merge": clo.merge_tile, "setop": clo.setop_tile,
+             "select": clo.select_tile}[family](ks, vs)
     assert t > 0
     return int(t)
 
@@ -296,6 +312,18 @@ def hist_limits(ss):
     assert L > 256
     return (32 << 10) // (32 * ss), L
 
+
+def search_limits(ks):
+    """(P, L): the pivots of the general path's sampled table and the longest haystack range staged in LDS."""
+    import cl_ops_amd as clo
+    P, L = int(clo.search_pivots(ks)), int(clo.search_lds_keys(ks))
+    assert 2 <= P <= L
+    return P, L
+
+
+# the haystack sizes at which the search changes form
+_HAY_EDGES = [lambda P, L: 0, lambda P, L: 1, lambda P, L: P - 1, lambda P, L: P, lambda P, L: P + 1, lambda P, L: L - 1, lambda P, L: L,
+              lambda P, L: L + 1, lambda P, L: 2 * L + 5]
 
 _EDGE_SIZES = [lambda t: 0, lambda t: 1, lambda t: t - 1, lambda t: t, lambda t: t + 1, lambda t: 2 * t - 1, lambda t: 2 * t + 1, lambda t: 3 * t + 1]
 
@@ -350,6 +378,12 @@ def _object_for(family, rng, stratum):
     if family == "hist":
         vt, st = _HIST_CVT[stratum[2]]
         return (_HIST_KT[stratum[:2]], vt or "uint", st, bool(rng.integers(0, 2)))
+    if family == "search":
+        return (stratum[0],)
+    if family == "setop":
+        return (stratum[2], stratum[0], TM._VS[stratum[1]])
+    if family == "select":          # op and pred are arguments of every call: see _Selects
+        return (stratum[0], TSL._VS[stratum[1]])
     return (stratum[0], TM._VS[stratum[1]])
 
 
@@ -367,12 +401,26 @@ def compatible(family, obj):
         key = [k for k, v in _HIST_KT.items() if v == kt][0]
         cvts = [c for c, p in _HIST_CVT.items() if p == (vt, st)] + (["cnt_" + st] if st in ("uint", "ulong") else [])
         return [key + (c, b) for c in cvts for b in _HIST_BINS]
+    if family == "search":
+        return [(obj[0], upper, flag) for upper in (False, True) for flag in (False, True)]
+    if family == "setop":
+        return [(obj[1], m, obj[0]) for m in _MERGE_MODES if TM._VS[m] == obj[2]]
+    if family == "select":
+        return [(obj[0], m, cls) for m in TSL.MODES for cls in ("flagged", "cmp") if TSL._VS[m] == obj[1]] + \
+            ([(obj[0], "arg_no_keys", "flagged")] if obj[1] == 4 else [])
     return [(obj[0], m) for m in _MERGE_MODES if TM._VS[m] == obj[1]]
 
 
-def _draw_call(family, rng, stratum, obj, edge=None):
-    """Everything of one call but the object: plain numbers, strings and lists."""
+def _draw_call(family, rng, stratum, obj, edge=None, state=None):
+    """Everything of one call but the object: plain numbers, strings and lists. state: what select carries from case to
+    case (see _draw_select)."""
     c = {}
+    if family == "search":
+        return _draw_search(rng, stratum, edge)
+    if family == "setop":
+        return _draw_setop(rng, stratum, obj, edge)
+    if family == "select":
+        return _draw_select(rng, stratum, obj, edge, state)
     if family in ("rbk", "sbk"):
         kt, vt, st, op = obj[:4]
         kind = stratum[1]
@@ -430,10 +478,108 @@ def _draw_call(family, rng, stratum, obj, edge=None):
     return c
 
 
+HAY_KINDS = ["specials", "equal", "distinct", "tie_run"]          # tie_run: one run longer than L laid across a pivot position
+NEEDLE_KINDS = ["uniform", "hits", "neighbours", "below", "above", "one_key"]
+SETOP_RANGES = ["overlapping", "a_below_b", "b_below_a", "interleaved", "a_eq_b", "a_subset_b"]
+SETOP_RUNS = ["specials", "short", "distinct"]                     # + one long run in A, in B or in both: c["long"]
+SELECT_KEYS = ["specials", "uniform"]
+THRESHOLDS = ["present", "between", "least", "greatest"]
+
+
+def _draw_search(rng, stratum, edge):
+    kt, upper, flag = stratum
+    ks = _size(TSE._NP[kt])
+    tile = tile_of("search", ks, 0)
+    P, L = search_limits(ks)
+    if rng.random() < 0.4:
+        nh = _HAY_EDGES[int(rng.integers(0, len(_HAY_EDGES)))](P, L)
+        if rng.random() < 0.25:
+            nh = max(0, nh + int(rng.integers(-2, 3)))
+    else:
+        nh = _draw_n(rng, L)
+    nn = _draw_n(rng, tile, edge)
+    hay = str(rng.choice(HAY_KINDS[:3] + (["tie_run"] * 3 if nh >= L + 3 else [])))
+    tie = None
+    if hay == "tie_run":                                   # pivot k of the general path lies at k * numel_h / P
+        ln = L + 1 + int(rng.integers(0, min(L, nh - L - 2) + 1))
+        piv = int(rng.integers(1, P)) * nh // P
+        tie = (max(0, min(piv - int(rng.integers(0, ln)), nh - ln)), ln)
+    return dict(kt=kt, upper=upper, sorted=flag, nh=nh, nn=nn, tile=tile, L=L, P=P, hay=hay, tie=tie,
+                needles=str(rng.choice(NEEDLE_KINDS)) if nh else "uniform", data_seed=int(rng.integers(0, 1 << 30)),
+                offs=[_draw_off(rng, ks), _draw_off(rng, ks), _draw_off(rng, 4)])
+
+
+def _draw_setop(rng, stratum, obj, edge):
+    kt, mode, op = stratum
+    ks, vs = _size(TM._NP[kt]), obj[2]
+    tile = tile_of("setop", ks, vs)
+    na, nb = (0 if rng.random() < 0.08 else _draw_n(rng, tile) for _ in range(2))
+    to_a = bool(rng.integers(0, 2))
+    if edge is not None:
+        na, nb = (_draw_n(rng, tile, edge), nb) if to_a else (na, _draw_n(rng, tile, edge))
+    if na + nb == 0:         # (both empty: test_gpu_setop.py's thin-ABI test)
+        na, nb = (0, 1) if to_a else (1, 0)
+    ranges = str(rng.choice(SETOP_RANGES if na and nb else SETOP_RANGES[:4]))
+    if ranges == "a_eq_b":   # the size that was dealt an edge stays
+        na = nb = na if to_a else nb
+    elif ranges == "a_subset_b" and na > nb:
+        na, nb = nb, na
+    long = None              # (where, the run's length in A, in B): longer than two tiles, of different lengths in both
+    fits = [w for w, ok in (("a", na > 2 * tile + 1), ("b", nb > 2 * tile + 1), ("both", min(na, nb) > 2 * tile + 2)) if ok]
+    if fits and rng.random() < 0.7:
+        where = str(rng.choice(fits))
+        length = lambda n: 2 * tile + 1 + int(rng.integers(0, min(tile, n - 2 * tile - 1) + 1))
+        la, lb = length(na) if where != "b" else 0, length(nb) if where != "a" else 0
+        if la == lb:
+            la, lb = (la, lb + 1) if lb < nb else (la + 1, lb) if la < na else (la - 1, lb)
+        long = (where, la, lb)
+    has_v, has_k = mode in ("v4", "v8"), mode != "arg_only"
+    return dict(kt=kt, mode=mode, op=op, na=na, nb=nb, tile=tile, ranges=ranges, runs=str(rng.choice(SETOP_RUNS)), long=long,
+                pass_vb=bool(rng.integers(0, 2)), data_seed=int(rng.integers(0, 1 << 30)),
+                offs=[_draw_off(rng, ks), _draw_off(rng, vs if has_v else 0), _draw_off(rng, ks), _draw_off(rng, vs if has_v else 0),
+                      _draw_off(rng, ks if has_k else 0), _draw_off(rng, vs)])
+
+
+def _draw_select(rng, stratum, obj, edge, state):
+    """op and pred are dealt, not drawn, so that the committed seeds hold every (key type, pred) and every (op, pred):
+    a comparison takes the next pred in turn for its key type, and every pred takes the two ops in turn, counted over all
+    seeds in state. A case on the object of the case before keeps that case's (op, pred) half of the time when it may."""
+    kt, mode, cls = stratum
+    ks, vs = _size(TM._NP[kt]), obj[1]
+    tile = tile_of("select", ks, vs)
+    before = state["before"]
+    if before is not None and (before["pred"] == "flagged") == (cls == "flagged") and rng.random() < 0.5:
+        op, pred = before["op"], before["pred"]
+    else:
+        pred = "flagged"
+        if cls == "cmp":
+            turn = state.setdefault(("kt", kt), TM.KEY_TYPES.index(kt))
+            state[("kt", kt)] = turn + 1
+            pred = _SELECT_CMP[turn % len(_SELECT_CMP)]
+        turn = state.setdefault(("pred", pred), 0)
+        state[("pred", pred)] = turn + 1
+        op = TSL.OPS[turn % 2]
+    valued = mode in ("v4", "v8")
+    return dict(kt=kt, mode=mode, op=op, pred=pred, n=_draw_n(rng, tile, edge), tile=tile, pattern=str(rng.choice(TSL.PATTERNS)),
+                keys=str(rng.choice(SELECT_KEYS)), threshold=str(rng.choice(THRESHOLDS)) if cls == "cmp" else None, data_seed=int(rng.integers(0, 1 << 30)),
+                offs=[_draw_off(rng, ks), _draw_off(rng, vs if valued else 0), _draw_off(rng, 1 if cls == "flagged" else ks),
+                      _draw_off(rng, ks if mode in ("keys", "v4", "v8", "arg") else 0), _draw_off(rng, vs)])
+
+
 def draw_cases(family, seed):
     """The cases of one seed as plain descriptions. The seed's share of the family's strata (the list, shuffled once, is
     dealt to the seeds in turn) is walked in order, each with a new object; between them, at random places, as many cases
-    again reuse the object of the case before on a random stratum it can run, with a size of their own."""
+    again reuse the object of the case before on a random stratum it can run, with a size of their own. (select deals
+    its preds and ops in turn over ALL its seeds, so the seeds before this one are drawn first: still a function of
+    (family, seed) alone.)"""
+    state = {}
+    if family == "select":
+        for earlier in range(seed):
+            _draw_seed(family, earlier, state)
+    return _draw_seed(family, seed, state)
+
+
+def _draw_seed(family, seed, state):
     strata = STRATA[family]
     order = np.random.default_rng(_SALT[family]).permutation(len(strata))
     share = -(-len(strata) // SEEDS[family])
@@ -454,7 +600,8 @@ def draw_cases(family, seed):
             options = compatible(family, obj)
             stratum = options[int(rng.integers(0, len(options)))]
         c = {"family": family, "seed": seed, "case": i, "reuse": not fresh[i], "object": obj}
-        c.update(_draw_call(family, rng, stratum, obj, edges.get(i)))
+        state["before"] = cases[-1] if cases and not fresh[i] else None         # the case before, on the same object
+        c.update(_draw_call(family, rng, stratum, obj, edges.get(i), state))
         assert stratum_of(c) == stratum, (c, stratum)
         cases.append(c)
     return cases
@@ -477,6 +624,12 @@ def stratum_of(c):
         copies, L = hist_limits(_size(TH._NP[c["st"]]))
         cvt = "cnt_" + c["st"] if c["vt"] is None else "%s->%s" % (c["vt"], c["st"])
         return (info.bits // 8, int(info.min < 0), cvt, "copies" if c["num_bins"] <= copies else "peel" if c["num_bins"] <= L else "global")
+    if f == "search":
+        return (c["kt"], c["upper"], c["sorted"])
+    if f == "setop":
+        return (c["kt"], c["mode"], c["op"])
+    if f == "select":
+        return (c["kt"], c["mode"], "flagged" if c["pred"] == "flagged" else "cmp")
     return (c["kt"], c["mode"])
 
 
@@ -536,6 +689,146 @@ def merge_inputs(c):
     return both[to_a], both[~to_a]
 
 
+def _ubits(rng, n, ut):
+    """n uniform words of the unsigned type ut."""
+    return rng.integers(0, 1 << (8 * np.dtype(ut).itemsize), n, dtype=np.uint64).astype(ut)
+
+
+def key_of_order(o, dt):
+    """The inverse of merge_model.order_key: the keys of type dt whose order keys are o."""
+    dt = np.dtype(dt)
+    ut = np.dtype(TM._U[dt.itemsize])
+    o = np.ascontiguousarray(o, dtype=ut)
+    sign = ut.type(1 << (8 * ut.itemsize - 1))
+    if dt.kind == "u":
+        return o.view(dt).copy()
+    if dt.kind == "i":
+        return (o ^ sign).view(dt)
+    return np.where((o & sign) != 0, o ^ sign, ~o).view(dt)
+
+
+def search_inputs(c):
+    """(haystack, needles) of a search case: the haystack in the library's order, the needles too where the case
+    promises it."""
+    kt, nh, nn = c["kt"], c["nh"], c["nn"]
+    dt = np.dtype(TSE._NP[kt])
+    ut = np.dtype(TM._U[dt.itemsize])
+    rng = np.random.default_rng(c["data_seed"])
+    if c["hay"] == "specials":
+        hay = TM.keys_of_type(kt, nh, c["data_seed"])
+    elif c["hay"] == "equal":
+        hay = np.repeat(TM.keys_of_type(kt, 1, c["data_seed"]), nh)
+    else:
+        hay = sort_keys(_ubits(rng, nh, ut).view(dt))
+        if c["tie"]:
+            at, ln = c["tie"]
+            hay[at:at + ln] = hay[at]
+    oh = order_key(hay)
+    top = (1 << (8 * dt.itemsize)) - 1
+    kind = c["needles"]
+    if kind == "hits":
+        o = oh[rng.integers(0, nh, nn)]
+    elif kind == "neighbours":                              # +-1 in order-key space (it wraps at the ends)
+        o = oh[rng.integers(0, nh, nn)] + np.where(rng.random(nn) < 0.5, 1, top).astype(ut)
+    elif kind == "below":                                   # (a first key that is the type's least has nothing below it)
+        o = rng.integers(0, max(int(oh[0]), 1), nn, dtype=np.uint64).astype(ut)
+    elif kind == "above":
+        o = rng.integers(min(int(oh[-1]) + 1, top), top, nn, dtype=np.uint64, endpoint=True).astype(ut)
+    else:
+        o = order_key(_ubits(rng, nn, ut).view(dt))
+        if kind == "one_key":
+            o[rng.random(nn) < 0.9] = oh[rng.integers(0, nh)]
+    ndl = key_of_order(o, dt)
+    return hay, (sort_keys(ndl) if c["sorted"] else ndl)
+
+
+def _setop_keys(c, n, which):
+    """n sorted keys of a setop case; which numbers the draw (A and B take their keys from one pool)."""
+    kt, seed = c["kt"], c["data_seed"]
+    if c["runs"] == "specials":
+        return TM.keys_of_type(kt, n, seed + which)
+    dt = np.dtype(TM._NP[kt])
+    total = c["na"] + c["nb"]
+    distinct = max(2, total // 4) if c["runs"] == "short" else 4 * total + 2
+    pool = _ubits(np.random.default_rng(seed), distinct, TM._U[dt.itemsize])
+    return sort_keys(pool[np.random.default_rng([seed, which]).integers(0, distinct, n)].view(dt))
+
+
+def _long_run(keys, x, ln, seed):
+    """keys with ln elements somewhere replaced by the key x, in order again."""
+    if not ln:
+        return keys
+    at = int(np.random.default_rng([seed, ln]).integers(0, keys.size - ln + 1))
+    keys = keys.copy()
+    keys[at:at + ln] = x
+    return sort_keys(keys)
+
+
+def setop_inputs(c):
+    """(keys_a, keys_b) of a setop case, both in the library's order."""
+    na, nb, seed = c["na"], c["nb"], c["data_seed"]
+    _, la, lb = c["long"] or (None, 0, 0)
+    if c["ranges"] in ("a_eq_b", "a_subset_b"):              # the long run is B's, and A's through B
+        b = _setop_keys(c, nb, 1)
+        ln = min(max(la, lb), nb)
+        b = _long_run(b, b[nb // 2], ln, seed)
+        if c["ranges"] == "a_eq_b":
+            return b.copy(), b
+        return b[np.sort(np.random.default_rng(seed).permutation(nb)[:na])], b
+    if c["ranges"] == "overlapping":
+        a, b = _setop_keys(c, na, 1), _setop_keys(c, nb, 2)
+    else:
+        both = _setop_keys(c, na + nb, 1)
+        if c["ranges"] == "a_below_b":
+            a, b = both[:na], both[na:]
+        elif c["ranges"] == "b_below_a":
+            a, b = both[nb:], both[:nb]
+        else:
+            to_a = np.zeros(na + nb, bool)
+            to_a[np.random.default_rng(seed).permutation(na + nb)[:na]] = True
+            a, b = both[to_a], both[~to_a]
+    if c["long"]:
+        x = (a if la else b)[(na if la else nb) // 2]        # one key for both runs
+        a, b = _long_run(a, x, la, seed), _long_run(b, x, lb, seed + 1)
+    return a, b
+
+
+def select_inputs(c):
+    """(keys, flags or the threshold) of a select case, the typed sibling of test_gpu_select.py's inputs_for: the keep
+    pattern decides which elements are kept. By flags: a kept element's flag is any byte but 0. By comparison: the keys
+    come from a pool (the type's specials, or uniform words) that the threshold splits into those the pred keeps and the
+    others, and every element draws from its side; where one side is empty (nothing is below the type's least key) all
+    elements draw from the other, and the pattern gives way."""
+    kt, n, pred = c["kt"], c["n"], c["pred"]
+    dt = np.dtype(TM._NP[kt])
+    ut = np.dtype(TM._U[dt.itemsize])
+    rng = np.random.default_rng(c["data_seed"])
+    mask = TSL.mask_of(c["pattern"], n, c["tile"], c["data_seed"])
+    pool = np.unique(order_key(TM.keys_of_type(kt, 64, c["data_seed"]) if c["keys"] == "specials" else _ubits(rng, 4096, ut).view(dt)))
+    if pred == "flagged":
+        return key_of_order(pool[rng.integers(0, pool.size, n)], dt), np.where(mask, rng.integers(1, 256, n), 0).astype(np.uint8)
+    top = (1 << (8 * dt.itemsize)) - 1
+    if c["threshold"] == "present":
+        t = pool[rng.integers(0, pool.size)]
+    elif c["threshold"] == "between":                       # a key of the pool's inside that is then taken out of it
+        assert pool.size >= 3
+        t = pool[rng.integers(1, pool.size - 1)]
+        pool = pool[pool != t]
+    else:
+        t = ut.type(0 if c["threshold"] == "least" else top)
+        if rng.random() < 0.5:
+            pool = np.unique(np.append(pool, t))
+    sides = {"lt": pool < t, "le": pool <= t, "gt": pool > t, "ge": pool >= t, "eq": pool == t, "ne": pool != t}[pred]
+    kept, rest = pool[sides], pool[~sides]
+    if not kept.size or not rest.size:
+        kept = rest = pool
+    o = np.where(mask, kept[rng.integers(0, kept.size, n)], rest[rng.integers(0, rest.size, n)])
+    for side, there in ((kept, mask), (rest, ~mask)):       # a threshold of the pool occurs often on its side, not once in the pool's size
+        if (side == t).any():
+            o[there & (rng.random(n) < 0.2)] = t
+    return key_of_order(o, dt), key_of_order(np.array([t], ut), dt)[0]
+
+
 def _make_object(clo, ctx, family, obj):
     if family == "rbk":
         return clo.ReduceByKey(ctx, obj[0], obj[1], obj[2], op=obj[3])
@@ -543,7 +836,33 @@ def _make_object(clo, ctx, family, obj):
         return clo.ScanByKey(ctx, obj[0], obj[1], obj[2], op=obj[3], inclusive=obj[4])
     if family == "hist":
         return clo.Histogram(ctx, obj[0], obj[1], obj[2], options="accumulate" if obj[3] else None)
+    if family == "search":
+        return clo.Search(ctx, obj[0])
+    if family == "setop":
+        return clo.SetOp(obj[0], ctx, obj[1], obj[2])
+    if family == "select":
+        return _Selects(clo, ctx, obj[0], obj[1])
     return clo.Merge(ctx, obj[0], obj[1])
+
+
+class _Selects:
+    """The fuzz's object of the select family: the CloSelect objects of one (key type, value size), one per (op, pred)
+    asked for, all alive until the next object replaces this one. op and pred are arguments of clo_select_new, yet no
+    kernel is built for them (include/clo_select.h), so a case that keeps the (op, pred) of the case before reuses that
+    CloSelect and its workspace at a size of its own, and one that does not gets a second one next to it."""
+
+    def __init__(self, clo, ctx, kt, vs):
+        self.made, self.new = {}, lambda op, pred: clo.Select(op, pred, ctx, kt, vs)
+
+    def get(self, op, pred):
+        if (op, pred) not in self.made:
+            self.made[(op, pred)] = self.new(op, pred)
+        return self.made[(op, pred)]
+
+    def close(self):
+        for s in self.made.values():
+            s.close()
+        self.made = {}
 
 
 def _run_one(dev, c, handle):
@@ -560,9 +879,18 @@ def _run_one(dev, c, handle):
         keys, values, prior = hist_inputs(c)
         assert handle.accumulate == c["accumulate"]
         TH.run_case(dev, c["kt"], c["vt"], c["st"], keys, values, c["lower"], c["shift"], c["num_bins"], what, offs=tuple(c["offs"]), obj=handle, prefill=prior)
-    else:
+    elif f == "merge":
         a, b = merge_inputs(c)
         TM.run_merge(dev, c["kt"], a, b, c["mode"], what, offs=tuple(c["offs"]), obj=handle)
+    elif f == "search":
+        hay, ndl = search_inputs(c)
+        TSE.run_search(dev, c["kt"], hay, ndl, ((c["upper"], c["sorted"]),), what, offs=tuple(c["offs"]), obj=handle)
+    elif f == "setop":
+        a, b = setop_inputs(c)
+        TSO.run_setop(dev, c["op"], c["kt"], a, b, c["mode"], what, offs=tuple(c["offs"]), obj=handle, pass_vb=c["pass_vb"])
+    else:
+        keys, fot = select_inputs(c)
+        TSL.run_select(dev, c["op"], c["pred"], c["kt"], keys, fot, c["mode"], what, offs=tuple(c["offs"]), obj=handle.get(c["op"], c["pred"]))
 
 
 def _fuzz_family(gpu, family, seed):
@@ -603,3 +931,18 @@ def test_fuzz_histogram(gpu, seed):
 @pytest.mark.parametrize("seed", range(SEEDS["merge"]))
 def test_fuzz_merge(gpu, seed):
     _fuzz_family(gpu, "merge", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["search"]))
+def test_fuzz_search(gpu, seed):
+    _fuzz_family(gpu, "search", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["setop"]))
+def test_fuzz_setop(gpu, seed):
+    _fuzz_family(gpu, "setop", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["select"]))
+def test_fuzz_select(gpu, seed):
+    _fuzz_family(gpu, "select", seed)

@@ -2,9 +2,9 @@
 context: the threading contract of the reference (no locks, no mutable globals: an object is not re-entrant, distinct
 objects are independent — SURVEY §8b "Threading"). ctypes drops the GIL during a call, so the C drivers, their workspace
 caches and the run-time compiler really do run side by side here. Every result is checked bit for bit against numpy.
-The by-key sort, reduce by key, scan by key, histogram and merge run the same way (the adapters of
-test_gpu_by_key_queues.py: inputs, the device call, the host-data call and the model of each), and give their device
-memory back like the sorters and scanners."""
+The by-key sort, reduce by key, scan by key, histogram, merge, search, the set operations and select run the same way
+(the adapters of test_gpu_by_key_queues.py: inputs, the device call, the host-data call and the model of each), and
+give their device memory back like the sorters and scanners."""
 import threading
 
 import numpy as np
@@ -92,7 +92,7 @@ def test_distinct_objects_on_distinct_threads(clo):
 
 
 def _by_key_worker(clo, ctx, kind, seed, rounds, max_log2, errors):
-    """One object of one of the five by-key kinds on a queue of its own: random sizes, device data."""
+    """One object of one of the kinds of test_gpu_by_key_queues.py on a queue of its own: random sizes, device data."""
     name = kind.__name__.strip("_")
     try:
         rng = np.random.default_rng(seed)
@@ -129,6 +129,26 @@ def test_by_key_objects_on_distinct_threads(clo):
     workers += [threading.Thread(target=_sort_worker, args=(clo, ctx, "satradix", "uint", 46, 16, 21, errors)),
                 threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "ulong", 47, 16, 21, errors))]
     assert len(workers) == 7
+    for w in workers:
+        w.start()
+    for w in workers:
+        w.join(timeout=600)
+    assert not any(w.is_alive() for w in workers), "a worker is stuck"
+    assert errors == []
+    ctx.close()
+
+
+def test_search_setop_and_select_objects_on_distinct_threads(clo):
+    """Six threads in one process: a search with sorted needles, a set operation and a select next to a merge, one
+    satradix sorter and one scanner."""
+    import test_gpu_by_key_queues as K
+    ctx = clo.Context(0)
+    errors = []
+    workers = [threading.Thread(target=_by_key_worker, args=(clo, ctx, kind, 50 + i, 16, 21, errors))
+               for i, kind in enumerate((K._Search, K._SetOp, K._Select, K._Merge))]
+    workers += [threading.Thread(target=_sort_worker, args=(clo, ctx, "satradix", "uint", 56, 16, 21, errors)),
+                threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "ulong", 57, 16, 21, errors))]
+    assert len(workers) == 6
     for w in workers:
         w.start()
     for w in workers:
@@ -266,11 +286,22 @@ def test_by_key_objects_give_their_device_memory_back(clo):
     """The same for a by-key sorter (two numel x 8-byte pair buffers cached per sorter), a reduce by key, a scan by key, a
     histogram and a merge (a cached workspace each): created, used at 2^21 elements through the device and the host-data
     form, and destroyed, over and over."""
-    import torch
     import test_gpu_by_key_queues as K
+    _give_back(clo, (K._SortByKey, K._ReduceByKey, K._ScanByKey, K._Histogram, K._Merge))
+
+
+def test_search_setop_and_select_objects_give_their_device_memory_back(clo):
+    """And for a search (the tiles' ranges of the sorted-needles form), a set operation and a select (split points and
+    kept counts): a cached workspace each."""
+    import test_gpu_by_key_queues as K
+    _give_back(clo, (K._Search, K._SetOp, K._Select))
+
+
+def _give_back(clo, kinds):
+    import torch
     ctx = clo.Context(0)
     n = 1 << 21
-    kinds = [kind() for kind in (K._SortByKey, K._ReduceByKey, K._ScanByKey, K._Histogram, K._Merge)]
+    kinds = [kind() for kind in kinds]
     data = []
     for i, k in enumerate(kinds):
         ins = k.inputs(n, 60 + i)
