@@ -350,6 +350,46 @@ int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in,
 	void* keys_out, void* values_out, uint64_t* num_out, size_t numel, int key_size, int key_kind,
 	int value_size, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- top-k (new functionality: CloTopK, include/clo_topk.h) ----
+ * With m = min(k, numel): the first m elements of the stable ascending sort of keys_in[0, numel) (which
+ * CLO_HIP_TOPK_SMALLEST) or of the stable sort by the complemented order key (CLO_HIP_TOPK_LARGEST: the largest key
+ * first), in clo_hip_merge's order of key_kind (0 unsigned, 1 signed, 2 IEEE total order); the lower index comes first
+ * among equal keys, so where the m-th key has ties the tied elements with the lowest indices are taken. They go to rows
+ * [0, m) of keys_out and values_out in increasing input index (order CLO_HIP_TOPK_INPUT) or in the order of that sort
+ * (CLO_HIP_TOPK_SORTED, for m <= clo_hip_topk_sorted_max only); rows >= m are not written, the outputs need hold m rows
+ * only. kth_out (may be NULL; device memory, one key, aligned to key_size) receives the key of the m-th chosen element
+ * of that sort, with its original bits; with both outputs NULL it is all that is computed. value_size 0 (none), 4 or 8:
+ * opaque words; value_size 4 with values_in NULL: values_out[j] is the element's index (the arg form), keys_out may
+ * then be NULL. numel 0 or k 0: success, nothing is enqueued, no workspace is needed.
+ * CLO_HIP_EARGS before anything is enqueued: which, order or key_kind out of range, numel >= 2^32, keys_out, values_out
+ * and kth_out all NULL, values (in or out) with value_size 0, values_out NULL with value_size > 0, NULL values_in with
+ * value_size 8, keys_in NULL with numel > 0, a pointer not aligned to its element, SORTED with m above
+ * clo_hip_topk_sorted_max, a missing or misaligned workspace with m > 0. Sizes not built: CLO_HIP_EUNSUPPORTED. A
+ * workspace below clo_hip_topk_workspace_bytes(numel, key_size, value_size): CLO_HIP_EWORKSPACE. No output may overlap
+ * an input, another output or kth_out (not checked here: the driver does).
+ * Whatever the arrays hold, reads stay inside the inputs and writes inside rows [0, m) and kth_out.
+ * key_size digit sweeps of 8 bits, most significant first, each followed by one work-group that picks the digit holding
+ * the remaining rank; then the tiles' counts of keys before and equal to the m-th, one launch that turns both into
+ * offsets (CLO_HIP_TOPK_SCAN_TRIP tiles per trip of its loop), the compacting sweep and, for SORTED, one work-group that
+ * sorts the m rows in LDS. Every sweep reads all numel keys: the time does not depend on the data. No work-group waits
+ * for another; global atomic adds go to the 256-word digit tables in the workspace alone (cleared by a fill on
+ * `stream`); asynchronous on `stream`; nothing is allocated and the host never waits or reads anything back, so the call
+ * can be captured into a linear graph and replayed after the keys were rewritten. k is a host argument: it is baked into
+ * the captured launches.
+ * clo_hip_topk_tile: the elements per tile of the count and apply sweeps, 0 for sizes not built.
+ * clo_hip_topk_sorted_max: the largest m SORTED takes (at least 1024), 0 for sizes not built.
+ * clo_hip_topk_workspace_bytes is monotone in numel, 0 for numel 0 and a multiple of CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_TOPK_SMALLEST 0
+#define CLO_HIP_TOPK_LARGEST  1
+#define CLO_HIP_TOPK_INPUT  0
+#define CLO_HIP_TOPK_SORTED 1
+#define CLO_HIP_TOPK_SCAN_TRIP 2048
+size_t clo_hip_topk_tile(int key_size, int value_size);
+size_t clo_hip_topk_sorted_max(int key_size, int value_size);
+size_t clo_hip_topk_workspace_bytes(size_t numel, int key_size, int value_size);
+int clo_hip_topk(int which, int order, const void* keys_in, const void* values_in, void* keys_out, void* values_out, void* kth_out,
+	size_t numel, size_t k, int key_size, int key_kind, int value_size, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
