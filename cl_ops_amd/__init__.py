@@ -17,12 +17,12 @@ from .merge import Merge, merge_tile  # noqa: F401
 from .search import Search, search_tile, search_lds_keys, search_pivots  # noqa: F401
 from .setop import SetOp, setop_tile  # noqa: F401
 from .select import Select, select_tile  # noqa: F401
-from .topk import TopK, topk_tile, topk_sorted_max, TOPK_WHICH, TOPK_ORDERS  # noqa: F401
+from .topk import TopK, topk_tile, topk_sweep_groups, topk_sorted_max, TOPK_WHICH, TOPK_ORDERS  # noqa: F401
 
 __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profiler", "HipEventTimer",
            "ShardTransport", "ShardSort", "Rng", "rng_names", "ReduceByKey", "reduce_by_key_tile",
            "ScanByKey", "scan_by_key_tile", "Histogram", "histogram_tile", "histogram_lds_bins",
            "Merge", "merge_tile", "Search", "search_tile", "search_lds_keys", "search_pivots",
            "SetOp", "setop_tile", "Select", "select_tile",
-           "TopK", "topk_tile", "topk_sorted_max", "TOPK_WHICH", "TOPK_ORDERS",
+           "TopK", "topk_tile", "topk_sweep_groups", "topk_sorted_max", "TOPK_WHICH", "TOPK_ORDERS",
            "CLO_TYPES", "clo_type", "wait_for_events"]

@@ -463,6 +463,9 @@ inline int topk_cus() {   // of the current device, as the stream is taken to be
 	return c;
 }
 
+// the groups a digit sweep launches where the tile count does not limit it
+inline size_t topk_sweep_groups() { return (size_t) topk_cus() * TOPK_GROUPS_PER_CU; }
+
 #define TOPK_CHECK_LAUNCH() do { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int) e_; } while (0)
 
 template <typename TK, int KIND>
@@ -472,7 +475,7 @@ int topk_find(const topk_args& a, TK flip) {
 	unsigned* const tables = reinterpret_cast<unsigned*>(a.ws);
 	topk_state* const state = reinterpret_cast<topk_state*>(a.ws + TOPK_WS_TABLES);
 	const unsigned tiles = (unsigned) ((a.n + TILE - 1) / TILE);
-	size_t groups = (size_t) topk_cus() * TOPK_GROUPS_PER_CU;
+	size_t groups = topk_sweep_groups();
 	if (groups > tiles) groups = tiles;
 	const int kvec = topk_vec_ok<TK>(a.keys);
 	const hipError_t e = hipMemsetAsync(tables, 0, (size_t) PASSES * TOPK_DIGITS * sizeof(unsigned), a.s);
@@ -570,6 +573,8 @@ size_t clo_hip_topk_tile(int key_size, int value_size) {
 	if (!topk_key_size_ok(key_size) || !topk_value_size_ok(value_size)) return 0;
 	return topk_tile(key_size, value_size);
 }
+
+size_t clo_hip_topk_sweep_groups(void) { return topk_sweep_groups(); }
 
 size_t clo_hip_topk_sorted_max(int key_size, int value_size) {
 	if (!topk_key_size_ok(key_size) || !topk_value_size_ok(value_size)) return 0;

@@ -20,6 +20,7 @@ _sig("clo_topk_get_which", C.c_char_p, vp)
 _sig("clo_topk_get_order", C.c_char_p, vp)
 _sig("clo_hip_topk_tile", sz, ci, ci)
 _sig("clo_hip_topk_sorted_max", sz, ci, ci)
+_sig("clo_hip_topk_sweep_groups", sz)
 _sig("clo_hip_topk_workspace_bytes", sz, sz, ci, ci)
 _sig("clo_hip_topk", ci, ci, ci, vp, vp, vp, vp, vp, sz, sz, ci, ci, ci, vp, sz, vp)
 
@@ -32,6 +33,12 @@ def topk_tile(key_size, value_size=0):
     """Elements per tile of the count and apply kernels for keys of key_size and values of value_size (0: none) bytes;
     0 for sizes that are not built."""
     return lib.clo_hip_topk_tile(key_size, value_size)
+
+
+def topk_sweep_groups():
+    """The work-groups a digit sweep launches on the current device where its tile count (tiles of topk_tile(key_size)
+    keys) does not limit it; with more tiles than that a group takes several."""
+    return lib.clo_hip_topk_sweep_groups()
 
 
 def topk_sorted_max(key_size, value_size=0):

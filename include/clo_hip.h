@@ -377,6 +377,8 @@ int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in,
  * can be captured into a linear graph and replayed after the keys were rewritten. k is a host argument: it is baked into
  * the captured launches.
  * clo_hip_topk_tile: the elements per tile of the count and apply sweeps, 0 for sizes not built.
+ * clo_hip_topk_sweep_groups: the work-groups a digit sweep launches on the current device where the number of its tiles
+ * (of clo_hip_topk_tile(key_size, 0) keys) does not limit it; above that many tiles a group takes several, grid-stride.
  * clo_hip_topk_sorted_max: the largest m SORTED takes (at least 1024), 0 for sizes not built.
  * clo_hip_topk_workspace_bytes is monotone in numel, 0 for numel 0 and a multiple of CLO_HIP_WORKSPACE_ALIGN. */
 #define CLO_HIP_TOPK_SMALLEST 0
@@ -385,6 +387,7 @@ int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in,
 #define CLO_HIP_TOPK_SORTED 1
 #define CLO_HIP_TOPK_SCAN_TRIP 2048
 size_t clo_hip_topk_tile(int key_size, int value_size);
+size_t clo_hip_topk_sweep_groups(void);
 size_t clo_hip_topk_sorted_max(int key_size, int value_size);
 size_t clo_hip_topk_workspace_bytes(size_t numel, int key_size, int value_size);
 int clo_hip_topk(int which, int order, const void* keys_in, const void* values_in, void* keys_out, void* values_out, void* kth_out,

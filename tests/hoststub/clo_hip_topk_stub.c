@@ -21,6 +21,8 @@ size_t clo_hip_topk_tile(int key_size, int value_size) {
 	return (key_size > value_size ? key_size : value_size) <= 4 ? 8192 : 4096;
 }
 
+size_t clo_hip_topk_sweep_groups(void) { return 1024; }   /* 256 compute units, four groups each */
+
 size_t clo_hip_topk_sorted_max(int key_size, int value_size) {
 	if (!topk_key_size_ok(key_size) || !topk_value_size_ok(value_size)) return 0;
 	return TOPK_STUB_SORTED_MAX;

@@ -5,7 +5,11 @@ call, views off their alignment, the wrap trap), and the vectorised models agree
 generator's own odd inputs (NaN payloads, unsorted keys, wrapping sums). For search, the set operations and select:
 every haystack, needle, range, run and threshold kind is seen, every (key type, pred), (op, pred) and (op, form) of
 select is drawn, the inputs are in the library's order wherever the case promises it, and search_model, setop_model
-and select_model equal element-by-element loops written from the headers' definitions."""
+and select_model equal element-by-element loops written from the headers' definitions. For top-k: every key and cut
+kind, every (key type, which) and (form, order, which), a call whose keys can be loaded as vectors and whose values
+cannot (and the reverse), a cut inside a tie run that takes a whole tile of equal keys, tie runs across a tile edge with
+the cut before and behind the edge, no "sorted" case above the cap and none refused, and topk_model against a plain loop
+over (order key, index) pairs."""
 import numpy as np
 import pytest
 
@@ -16,8 +20,9 @@ from sbk_model import sbk, sbk_loop, identity
 from search_model import search
 from select_model import select
 from setop_model import setop
+from topk_model import topk
 
-FAMILIES = ["rbk", "sbk", "hist", "merge", "search", "setop", "select"]
+FAMILIES = ["rbk", "sbk", "hist", "merge", "search", "setop", "select", "topk"]
 _ALL = {}
 
 
@@ -35,6 +40,7 @@ def test_the_tables_hold_every_instantiation():
     assert len(F.STRATA["search"]) == 11 * 2 * 2 == 44
     assert len(F.STRATA["setop"]) == 11 * 5 * 4 == 220
     assert len(F.STRATA["select"]) == 11 * 5 * 2 + 11 == 121
+    assert len(F.STRATA["topk"]) == 11 * (5 * 2 + 1) == 121
     for f in FAMILIES:
         assert len(set(F.STRATA[f])) == len(F.STRATA[f])
         assert F.SEEDS[f] * F.CASES[f] >= 2 * len(F.STRATA[f])
@@ -378,3 +384,100 @@ def test_select_cases():
     assert looped >= len(cases) // 6
     assert seen >= {"between two keys that occur", "least, among the keys", "least, below every key", "greatest, among the keys", "greatest, above every key",
                     "the pattern kept by a comparison"}, seen
+
+
+def topk_loop(which, order, keys, k):
+    """clo_topk.h: the first m = min(k, numel) of the stable sort by the key's order (unsigned by bits, signed by value,
+    IEEE by sign, then magnitude bits: -0 below +0, NaNs at the ends by payload), the largest first for "largest", the
+    lower index first among equal keys; in that order or by index. (rows, the index of the m-th chosen element)."""
+    dt = keys.dtype
+    if dt.kind == "f":
+        bits = 8 * dt.itemsize
+        mag = lambda raw: raw & ((1 << (bits - 1)) - 1)
+        o = [-(mag(raw) + 1) if raw >> (bits - 1) else mag(raw) for raw in keys.view("u%d" % dt.itemsize).tolist()]
+    else:
+        o = [int(x) for x in keys.tolist()]
+    pairs = sorted((-x if which == "largest" else x, i) for i, x in enumerate(o))[:min(k, len(o))]
+    rows = [i for _, i in pairs]
+    return (sorted(rows) if order == "input" else rows), (rows[-1] if rows else None)
+
+
+def test_topk_cases():
+    cases = cases_of("topk")
+    kts, W = F.TM.KEY_TYPES, F.TT.WHICH
+    assert len(cases) == 4 * 62 == 248
+    assert {c["keys"] for c in cases} == set(F.TOPK_KEYS) and {c["cut"] for c in cases} == set(F.TOPK_CUTS)
+    assert {(c["kt"], c["which"]) for c in cases} == {(kt, w) for kt in kts for w in W}                                # the 22
+    forms = {(m, o, w) for m in F.TT.MODES for o in F.TT.ORDERS for w in W} | {("kth_only", None, w) for w in W}       # the 22
+    assert {F.stratum_of(c)[1:] + (c["which"],) for c in cases} == forms
+    assert all(c["kth"] for c in cases if c["mode"] == "kth_only") and all(c["order"] == "input" for c in cases if c["mode"] == "kth_only")
+    for m in F.TT.MODES:                                   # kth_out given and NULL next to every form
+        assert {c["kth"] for c in cases if c["mode"] == m} == {False, True}, m
+    assert {c["digit"] for c in cases if c["keys"] == "one_digit"} >= set(range(8))                     # every digit of the widest key
+    # a CloTopK really reused: the (which, order) of the case before on the same object, at a size of its own
+    again = [(a, b) for a, b in zip(cases, cases[1:]) if b["reuse"] and (a["which"], a["order"]) == (b["which"], b["order"])]
+    assert len(again) >= 20 and any(b["n"] > 4 * a["n"] > 0 for a, b in again) and any(a["n"] > 4 * b["n"] > 0 for a, b in again)
+    # keys that vector loads take and values that they do not, and the reverse: kvec and vvec are decided apart
+    for m in ("v4", "v8"):
+        mixed = {(c["offs"][0] % 16 == 0, c["offs"][1] % 16 == 0) for c in cases if c["mode"] == m and c["n"] > c["tile"]}
+        assert mixed >= {(True, False), (False, True)}, (m, mixed)
+    # kth_out at an odd offset of a multi-byte key next to outputs on a 16-byte boundary
+    assert any(c["kth"] and c["offs"][4] % 16 and c["offs"][2] % 16 == 0 and c["offs"][3] % 16 == 0 and c["mode"] in ("v4", "v8", "arg") for c in cases)
+    seen, looped, calls, at_cap = set(), 0, 0, 0
+    for c in cases:
+        keys, k = F.topk_inputs(c)
+        n, tile, which, order = c["n"], c["tile"], c["which"], c["order"]
+        dt = np.dtype(F.TM._NP[c["kt"]])
+        assert keys.size == n and keys.dtype == dt and keys.flags.c_contiguous and k >= 0
+        assert F.topk_inputs(c)[1] == k                                    # the GPU runner resolves the same cut
+        m = min(k, n)
+        if order == "sorted":                                              # never refused ...
+            assert m <= c["cap"], c
+            at_cap += m == c["cap"]
+        calls += m > 0
+        assert m > 0 or n == 0 or k == 0, c                                # ... and every other case is a device call
+        if dt.kind == "f" and n:
+            b = keys.view("u%d" % dt.itemsize)
+            seen.update(("nan payloads",) if len(set(b[np.isnan(keys)].tolist())) > 2 else ())
+            seen.update(("both zeros",) if len(set(b[keys == 0].tolist())) > 1 else ())
+        x = order_key(keys)
+        x = ~x if which == "largest" else x
+        if c["keys"] == "reversed" and n > 100 and which == "smallest" and bool(np.all(x[:-1] >= x[1:])):
+            seen.add("the winners at the end")
+        if c["keys"] == "one_digit" and n > 1000:
+            assert np.unique(x).size <= 256 and np.unique(x >> x.dtype.type(8 * c["digit"])).size <= 256 and np.unique(x).size > 100
+        if c["keys"] == "few":
+            assert np.unique(x).size <= 5
+        if m:
+            t = np.sort(x)[m - 1]
+            eq = np.flatnonzero(x == t)                                    # the tie run of the k-th key, by index
+            take = m - int((x < t).sum())                                  # how many of it are taken
+            assert 1 <= take <= eq.size
+            kinds = {"run_first": take == 1, "run_last": take == eq.size, "next_run_first": take == 1 or k > n, "run_inside": 1 < take < eq.size or eq.size < 3}
+            if c["cut"] in kinds and not (order == "sorted" and m == c["cap"]):
+                assert kinds[c["cut"]], c
+            if 1 < take < eq.size:
+                seen.add("a cut strictly inside a run")
+                if c["mode"] != "kth_only" and order == "input" and eq.size > 2 * tile and take >= tile and eq[0] // tile == 0:
+                    seen.add("a whole tile of equal keys is taken")       # room >= the tile in the run's first tile
+            if c["mode"] != "kth_only" and take < eq.size and eq[0] // tile != eq[-1] // tile:
+                last = eq[take - 1]                                        # the last equal element taken
+                if last // tile == eq[0] // tile:
+                    seen.add("the cut before the tile edge")
+                else:
+                    seen.add("the cut behind the tile edge")
+                if eq[take] // tile != last // tile:
+                    seen.add("the cut on the tile edge")
+            if c["mode"] != "kth_only" and n > 2 * tile and take == eq.size and eq[0] // tile != eq[-1] // tile:
+                seen.add("all of a run across tiles")
+        if n <= 5000:
+            looped += 1
+            for o in ((order,) if c["mode"] != "kth_only" else F.TT.ORDERS):
+                p, kth = topk(which, o, keys, k)
+                rows, last = topk_loop(which, o, keys, k)
+                assert p.tolist() == rows, c
+                assert kth.tobytes() == (keys[last:last + 1].tobytes() if rows else b""), c
+    assert looped >= len(cases) // 6
+    assert calls >= 200 and at_cap >= 2, (calls, at_cap)
+    assert seen >= {"nan payloads", "both zeros", "the winners at the end", "a cut strictly inside a run", "a whole tile of equal keys is taken",
+                    "the cut before the tile edge", "the cut behind the tile edge", "all of a run across tiles"}, seen

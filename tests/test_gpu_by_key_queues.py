@@ -1,4 +1,4 @@
-"""The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram, CloMerge, CloSearch, CloSetOp and CloSelect on the queue
+"""The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram, CloMerge, CloSearch, CloSetOp, CloSelect and CloTopK on the queue
 production uses (no profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace
 belongs to one queue at a time"): one object is called six times on two live queues in turn, with no host
 synchronisation between the calls and sizes that make it reuse and outgrow its workspace mid-sequence; then the queue of
@@ -16,6 +16,7 @@ from sbk_model import sbk
 from search_model import search
 from select_model import select
 from setop_model import setop
+from topk_model import topk
 from test_gpu_reduce_by_key import structure, make_keys, make_values
 
 pytestmark = pytest.mark.gpu
@@ -222,6 +223,67 @@ class _Select:
         return ko, vo, np.array([k], np.uint64)
 
 
+class _TopK:
+    """The n // 3 + 1 largest of n uint keys with many ties (3000 values: the cut falls inside a tie run), in input
+    order, uint values carried along. A call makes 2 * 4 + 3 dependent launches that talk through the object's
+    workspace: the digit tables (cleared by a fill on the queue), the states and the tiles' counts.
+    -> (keys_out, values_out, kth_out)."""
+    out_types = (np.uint32, np.uint32, np.uint32)
+    which, order = "largest", "input"
+
+    def new(self, clo, ctx):
+        return clo.TopK(self.which, self.order, ctx, "uint", 4)
+
+    def k(self, n):
+        return n // 3 + 1
+
+    def inputs(self, n, seed):
+        rng = np.random.default_rng(seed)
+        return rng.integers(0, 3000, n).astype(np.uint32), rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+
+    def out_counts(self, ins):
+        m = min(self.k(ins[0].size), ins[0].size)
+        return m, m, 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], i[1], o[0], o[1], o[2], ins[0].size, self.k(ins[0].size))
+
+    def want(self, ins):
+        p, kth = topk(self.which, self.order, ins[0], self.k(ins[0].size))
+        return ins[0][p], ins[1][p], kth
+
+    def host(self, obj, q, ins):
+        ko, vo, kth = obj.with_host_data(ins[0], self.k(ins[0].size), ins[1], q_exec=q)
+        return ko, vo, np.array([kth], np.uint32)
+
+
+class _TopKSortedArg(_TopK):
+    """The 1000 smallest of the same keys (below the cap of the sorted order) in the order of the sort, as indices with
+    keys_out, kth_out not asked for: the sort kernel behind the apply sweep. -> (keys_out, the indices)."""
+    out_types = (np.uint32, np.uint32)
+    which, order = "smallest", "sorted"
+
+    def k(self, n):
+        return 1000
+
+    def inputs(self, n, seed):
+        return _TopK.inputs(self, n, seed)[:1]
+
+    def out_counts(self, ins):
+        return _TopK.out_counts(self, ins)[:2]
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], None, o[0], o[1], None, ins[0].size, self.k(ins[0].size))
+
+    def want(self, ins):
+        p, _ = topk(self.which, self.order, ins[0], self.k(ins[0].size))
+        return ins[0][p], p
+
+    def host(self, obj, q, ins):
+        ko, vo, _ = obj.with_host_data(ins[0], self.k(ins[0].size), kth=False, q_exec=q)
+        return ko, vo
+
+
 def _same(got, want, what):
     assert len(got) == len(want)
     for k, (g, w) in enumerate(zip(got, want)):
@@ -229,7 +291,7 @@ def _same(got, want, what):
             "%s: output %d differs from the model" % (what, k)
 
 
-@pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge, _Search, _SetOp, _Select], ids=lambda k: k.__name__.strip("_"))
+@pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge, _Search, _SetOp, _Select, _TopK, _TopKSortedArg], ids=lambda k: k.__name__.strip("_"))
 def test_object_moves_between_queues(gpu, kind):
     import cl_ops_amd as clo
     ctx, _ = gpu

@@ -3,8 +3,8 @@ every path boundary (one-launch sorts, single-sweep passes, 8 192- and 16 384-el
 tiles), every radix, element types, in place / out of place, stable pairs — against
 numpy. Everything goes through the C-ABI of libcl_ops_hip.so.
 
-The second half is the STRATIFIED fuzz of reduce by key, scan by key, histogram, merge, search, the set operations and
-select: the kernels of those seven are templates over (key size or type x value -> sum conversion, value form x op, mode
+The second half is the STRATIFIED fuzz of reduce by key, scan by key, histogram, merge, search, the set operations,
+select and top-k: the kernels of those eight are templates over (key size or type x value -> sum conversion, value form x op, mode
 or path), and draw_cases() walks the list of those instantiations, written out below from the public type rules, so that
 the committed seeds together launch every one; sizes, run structures, bounds, layouts, thresholds, view offsets and the
 reuse of one object over a random sequence of sizes are random per case. draw_cases() and the *_inputs() functions touch
@@ -23,6 +23,7 @@ import test_gpu_scan_by_key as TS
 import test_gpu_search as TSE
 import test_gpu_select as TSL
 import test_gpu_setop as TSO
+import test_gpu_topk as TT
 from merge_model import order_key, sort_keys
 
 pytestmark = pytest.mark.gpu
@@ -251,7 +252,7 @@ def test_fuzz_sharded_sort_loopback(gpu, seed):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# The stratified fuzz of the seven families
+# The stratified fuzz of the eight families
 # ----------------------------------------------------------------------------------------------------------------------
 
 _KT_BY_SIZE = {1: ["uchar"], 2: ["ushort"], 4: ["uint", "int", "float"], 8: ["ulong", "double"]}     # reduce / scan by key
@@ -268,7 +269,9 @@ _SELECT_CMP = list(TSL.PREDS[1:])
 # clo_histogram.h, clo_merge.h, clo_search.h, clo_setop.h, clo_select.h; DESIGN.md for the three forms of the
 # histogram), not from the kernels' enums. search: (key type, upper, NEEDLES_SORTED); setop: (key type, value mode, op);
 # select: (key type, value form, by flags | by comparison), the indices of the set flags without keys_in being a form of
-# the flagged selection alone.
+# the flagged selection alone. topk (include/clo_topk.h): (key type, value form, order), the "sorted" order with its own
+# kernel per (key size, value size) that reads the keys from the workspace where keys_out is not given (arg_only), and
+# the k-th key alone, which stops after the digit sweeps and has no order.
 STRATA = {
     "rbk": [(ks, kind) for ks in (1, 2, 4, 8) for kind in ["keys_only"] + _BK_KINDS],
     "sbk": [(ks, kind, incl) for ks in (1, 2, 4, 8) for kind in _BK_KINDS for incl in (False, True)],
@@ -277,12 +280,13 @@ STRATA = {
     "search": [(kt, upper, flag) for kt in TSE.KEY_TYPES for upper in (False, True) for flag in (False, True)],
     "setop": [(kt, mode, op) for kt in TM.KEY_TYPES for mode in _MERGE_MODES for op in TSO.OPS],
     "select": [(kt, mode, cls) for kt in TM.KEY_TYPES for mode in TSL.MODES for cls in ("flagged", "cmp")] + [(kt, "arg_no_keys", "flagged") for kt in TM.KEY_TYPES],
+    "topk": [(kt, mode, order) for kt in TM.KEY_TYPES for mode in TT.MODES for order in TT.ORDERS] + [(kt, "kth_only", None) for kt in TM.KEY_TYPES],
 }
 # seeds x cases >= 2 x strata: half the cases of a seed open a new stratum (with a new object), the other half reuse
 # the object of the case before them on a stratum it can run
-SEEDS = {"rbk": 2, "sbk": 3, "hist": 4, "merge": 2, "search": 2, "setop": 8, "select": 4}
-CASES = {"rbk": 60, "sbk": 76, "hist": 72, "merge": 60, "search": 60, "setop": 60, "select": 62}
-_SALT = {"rbk": 61, "sbk": 62, "hist": 63, "merge": 64, "search": 65, "setop": 66, "select": 67}
+SEEDS = {"rbk": 2, "sbk": 3, "hist": 4, "merge": 2, "search": 2, "setop": 8, "select": 4, "topk": 4}
+CASES = {"rbk": 60, "sbk": 76, "hist": 72, "merge": 60, "search": 60, "setop": 60, "select": 62, "topk": 62}
+_SALT = {"rbk": 61, "sbk": 62, "hist": 63, "merge": 64, "search": 65, "setop": 66, "select": 67, "topk": 68}
 
 
 def _size(x):
@@ -300,7 +304,7 @@ def tile_of(family, ks, vs):
         t = clo.search_tile(ks)                       # needles per tile
     else:
         t = {"rbk": clo.reduce_by_key_tile, "sbk": clo.scan_by_key_tile, "hist": clo.histogram_tile, "merge": clo.merge_tile, "setop": clo.setop_tile,
-             "select": clo.select_tile}[family](ks, vs)
+             "select": clo.select_tile, "topk": clo.topk_tile}[family](ks, vs)
     assert t > 0
     return int(t)
 
@@ -384,6 +388,8 @@ def _object_for(family, rng, stratum):
         return (stratum[2], stratum[0], TM._VS[stratum[1]])
     if family == "select":          # op and pred are arguments of every call: see _Selects
         return (stratum[0], TSL._VS[stratum[1]])
+    if family == "topk":            # which and order are arguments of clo_topk_new: see _TopKs
+        return (stratum[0], TT._VS[stratum[1]])
     return (stratum[0], TM._VS[stratum[1]])
 
 
@@ -408,12 +414,14 @@ def compatible(family, obj):
     if family == "select":
         return [(obj[0], m, cls) for m in TSL.MODES for cls in ("flagged", "cmp") if TSL._VS[m] == obj[1]] + \
             ([(obj[0], "arg_no_keys", "flagged")] if obj[1] == 4 else [])
+    if family == "topk":
+        return [(obj[0], m, order) for m in TT.MODES for order in TT.ORDERS if TT._VS[m] == obj[1]] + ([(obj[0], "kth_only", None)] if obj[1] == 0 else [])
     return [(obj[0], m) for m in _MERGE_MODES if TM._VS[m] == obj[1]]
 
 
 def _draw_call(family, rng, stratum, obj, edge=None, state=None):
-    """Everything of one call but the object: plain numbers, strings and lists. state: what select carries from case to
-    case (see _draw_select)."""
+    """Everything of one call but the object: plain numbers, strings and lists. state: what select and topk carry from
+    case to case (see _draw_select, _draw_topk)."""
     c = {}
     if family == "search":
         return _draw_search(rng, stratum, edge)
@@ -421,6 +429,8 @@ def _draw_call(family, rng, stratum, obj, edge=None, state=None):
         return _draw_setop(rng, stratum, obj, edge)
     if family == "select":
         return _draw_select(rng, stratum, obj, edge, state)
+    if family == "topk":
+        return _draw_topk(rng, stratum, obj, edge, state)
     if family in ("rbk", "sbk"):
         kt, vt, st, op = obj[:4]
         kind = stratum[1]
@@ -484,6 +494,9 @@ SETOP_RANGES = ["overlapping", "a_below_b", "b_below_a", "interleaved", "a_eq_b"
 SETOP_RUNS = ["specials", "short", "distinct"]                     # + one long run in A, in B or in both: c["long"]
 SELECT_KEYS = ["specials", "uniform"]
 THRESHOLDS = ["present", "between", "least", "greatest"]
+TOPK_KEYS = ["specials", "uniform", "few", "one_digit", "sorted", "reversed"]
+# k itself, a uniform rank, or a place in the tie run of the key at a drawn rank of the sort (topk_inputs resolves it)
+TOPK_CUTS = ["k=0", "k=1", "k=2", "k=n-1", "k=n", "k=n+1", "k=10n", "rank", "run_first", "run_inside", "run_last", "next_run_first"]
 
 
 def _draw_search(rng, stratum, edge):
@@ -566,14 +579,46 @@ def _draw_select(rng, stratum, obj, edge, state):
                       _draw_off(rng, ks if mode in ("keys", "v4", "v8", "arg") else 0), _draw_off(rng, vs)])
 
 
+def _draw_topk(rng, stratum, obj, edge, state):
+    """which is dealt, not drawn, so that the committed seeds hold every (key type, which) and every (form, order,
+    which): a case takes the direction that its key type and its (form, order) together have seen less often, counted
+    over all seeds in state. A case on the object of the case before keeps that case's which half of the time when its
+    order is the same: it then runs on the same CloTopK. The k-th key alone is asked of an "input" object. The byte that
+    varies in "one_digit" keys is dealt as well."""
+    kt, mode, order = stratum
+    order = order or "input"
+    ks, vs = _size(TM._NP[kt]), obj[1]
+    tile = tile_of("topk", ks, vs)
+    before = state["before"]
+    seen = state.setdefault("which", {})
+    if before is not None and before["order"] == order and rng.random() < 0.5:
+        which = before["which"]
+    else:
+        turn = state["turn"] = state.get("turn", -1) + 1
+        load = lambda w: (seen.get((kt, w), 0) + seen.get((mode, order, w), 0), seen.get((kt, w), 0), (TT.WHICH.index(w) + turn) % 2)
+        which = min(TT.WHICH, key=load)
+    for what in ((kt, which), (mode, order, which)):
+        seen[what] = seen.get(what, 0) + 1
+    import cl_ops_amd as clo
+    keys = str(rng.choice(TOPK_KEYS))
+    digit = None
+    if keys == "one_digit":                                 # the varying byte is dealt too: a key size takes its bytes in turn
+        digit = state[("digit", ks)] = (state.get(("digit", ks), -1) + 1) % ks
+    return dict(kt=kt, mode=mode, order=order, which=which, n=_draw_n(rng, tile, edge), tile=tile, cap=int(clo.topk_sorted_max(ks, vs)), keys=keys,
+                digit=digit, cut=str(rng.choice(TOPK_CUTS)), cut_u=[float(rng.random()), float(rng.random())],
+                kth=bool(mode == "kth_only" or rng.integers(0, 2)), data_seed=int(rng.integers(0, 1 << 30)),
+                offs=[_draw_off(rng, ks), _draw_off(rng, vs if mode in ("v4", "v8") else 0), _draw_off(rng, ks if mode in ("keys", "v4", "v8", "arg") else 0),
+                      _draw_off(rng, vs), _draw_off(rng, ks)])
+
+
 def draw_cases(family, seed):
     """The cases of one seed as plain descriptions. The seed's share of the family's strata (the list, shuffled once, is
     dealt to the seeds in turn) is walked in order, each with a new object; between them, at random places, as many cases
     again reuse the object of the case before on a random stratum it can run, with a size of their own. (select deals
-    its preds and ops in turn over ALL its seeds, so the seeds before this one are drawn first: still a function of
-    (family, seed) alone.)"""
+    its preds and ops, and topk its directions, in turn over ALL the family's seeds, so the seeds before this one are
+    drawn first: still a function of (family, seed) alone.)"""
     state = {}
-    if family == "select":
+    if family in ("select", "topk"):
         for earlier in range(seed):
             _draw_seed(family, earlier, state)
     return _draw_seed(family, seed, state)
@@ -630,6 +675,8 @@ def stratum_of(c):
         return (c["kt"], c["mode"], c["op"])
     if f == "select":
         return (c["kt"], c["mode"], "flagged" if c["pred"] == "flagged" else "cmp")
+    if f == "topk":                 # (with neither output the call ends after the digit sweeps, whatever the object's order)
+        return (c["kt"], c["mode"], None if c["mode"] == "kth_only" else c["order"])
     return (c["kt"], c["mode"])
 
 
@@ -829,6 +876,50 @@ def select_inputs(c):
     return key_of_order(o, dt), key_of_order(np.array([t], ut), dt)[0]
 
 
+def topk_inputs(c):
+    """(keys, k) of a topk case. The cut is resolved here, on the keys: a rank r of the sort in the case's direction is
+    drawn below numel (for "sorted" below the cap too), and k takes the first element of the tie run of the key at r, an
+    element strictly inside it (the first where the run has fewer than three), its last, or the first of the next run.
+    Where a "sorted" case then has min(k, numel) above the cap, k is the cap: no case is refused."""
+    kt, n, cut = c["kt"], c["n"], c["cut"]
+    dt = np.dtype(TM._NP[kt])
+    ut = np.dtype(TM._U[dt.itemsize])
+    rng = np.random.default_rng(c["data_seed"])
+    if c["keys"] == "specials":
+        keys = rng.permutation(TM.keys_of_type(kt, n, c["data_seed"]))
+    elif c["keys"] == "uniform":
+        keys = _ubits(rng, n, ut).view(dt)
+    elif c["keys"] == "few":                                # ties that run over every tile
+        pool = _ubits(rng, int(rng.integers(2, 6)), ut)
+        keys = pool[rng.integers(0, pool.size, n)].view(dt)
+    elif c["keys"] == "one_digit":                          # one byte of the order key varies
+        shift = 8 * c["digit"]
+        rest = int(_ubits(rng, 1, ut)[0]) & ~(0xFF << shift)
+        keys = key_of_order((rng.integers(0, 256, n, dtype=np.uint64) << np.uint64(shift) | np.uint64(rest)).astype(ut), dt)
+    else:                                                   # in the library's order, ascending or descending, with ties
+        pool = _ubits(rng, n // 3 + 1, ut).view(dt)
+        keys = sort_keys(pool[rng.integers(0, pool.size, n)])
+        if c["keys"] == "reversed":
+            keys = keys[::-1]
+    keys = np.ascontiguousarray(keys)
+    fixed = {"k=0": 0, "k=1": 1, "k=2": 2, "k=n-1": max(n - 1, 0), "k=n": n, "k=n+1": n + 1, "k=10n": 10 * n}
+    lim = min(n, c["cap"]) if c["order"] == "sorted" else n
+    if cut in fixed:
+        k = fixed[cut]
+    elif not lim:
+        k = 1
+    else:
+        x = order_key(keys)
+        xs = np.sort(~x if c["which"] == "largest" else x)
+        r = int(c["cut_u"][0] * lim)
+        lo, hi = int(np.searchsorted(xs, xs[r], "left")), int(np.searchsorted(xs, xs[r], "right"))     # the run holds ranks lo .. hi - 1
+        k = {"rank": r + 1, "run_first": lo + 1, "run_inside": lo + 2 + int(c["cut_u"][1] * (hi - lo - 2)) if hi - lo >= 3 else lo + 1,
+             "run_last": hi, "next_run_first": hi + 1}[cut]
+    if c["order"] == "sorted" and min(k, n) > c["cap"]:
+        k = c["cap"]
+    return keys, int(k)
+
+
 def _make_object(clo, ctx, family, obj):
     if family == "rbk":
         return clo.ReduceByKey(ctx, obj[0], obj[1], obj[2], op=obj[3])
@@ -842,6 +933,8 @@ def _make_object(clo, ctx, family, obj):
         return clo.SetOp(obj[0], ctx, obj[1], obj[2])
     if family == "select":
         return _Selects(clo, ctx, obj[0], obj[1])
+    if family == "topk":
+        return _TopKs(clo, ctx, obj[0], obj[1])
     return clo.Merge(ctx, obj[0], obj[1])
 
 
@@ -863,6 +956,16 @@ class _Selects:
         for s in self.made.values():
             s.close()
         self.made = {}
+
+
+class _TopKs(_Selects):
+    """The same for topk: the CloTopK objects of one (key type, value size), one per (which, order) asked for. which and
+    order are arguments of clo_topk_new (include/clo_topk.h), so a case that keeps the (which, order) of the case before
+    reuses that CloTopK and its workspace (the digit tables, states and counts of the call before still in it) at a size
+    of its own."""
+
+    def __init__(self, clo, ctx, kt, vs):
+        self.made, self.new = {}, lambda which, order: clo.TopK(which, order, ctx, kt, vs)
 
 
 def _run_one(dev, c, handle):
@@ -888,6 +991,10 @@ def _run_one(dev, c, handle):
     elif f == "setop":
         a, b = setop_inputs(c)
         TSO.run_setop(dev, c["op"], c["kt"], a, b, c["mode"], what, offs=tuple(c["offs"]), obj=handle, pass_vb=c["pass_vb"])
+    elif f == "topk":
+        keys, k = topk_inputs(c)
+        TT.run_topk(dev, c["which"], c["order"], c["kt"], keys, k, c["mode"], what + ", %s keys, cut %s" % (c["keys"], c["cut"]), offs=tuple(c["offs"]),
+                    obj=handle.get(c["which"], c["order"]), kth=c["kth"])
     else:
         keys, fot = select_inputs(c)
         TSL.run_select(dev, c["op"], c["pred"], c["kt"], keys, fot, c["mode"], what, offs=tuple(c["offs"]), obj=handle.get(c["op"], c["pred"]))
@@ -946,3 +1053,8 @@ def test_fuzz_setop(gpu, seed):
 @pytest.mark.parametrize("seed", range(SEEDS["select"]))
 def test_fuzz_select(gpu, seed):
     _fuzz_family(gpu, "select", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["topk"]))
+def test_fuzz_topk(gpu, seed):
+    _fuzz_family(gpu, "topk", seed)

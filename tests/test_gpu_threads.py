@@ -2,7 +2,7 @@
 context: the threading contract of the reference (no locks, no mutable globals: an object is not re-entrant, distinct
 objects are independent — SURVEY §8b "Threading"). ctypes drops the GIL during a call, so the C drivers, their workspace
 caches and the run-time compiler really do run side by side here. Every result is checked bit for bit against numpy.
-The by-key sort, reduce by key, scan by key, histogram, merge, search, the set operations and select run the same way
+The by-key sort, reduce by key, scan by key, histogram, merge, search, the set operations, select and top-k run the same way
 (the adapters of test_gpu_by_key_queues.py: inputs, the device call, the host-data call and the model of each), and
 give their device memory back like the sorters and scanners."""
 import threading
@@ -158,6 +158,27 @@ def test_search_setop_and_select_objects_on_distinct_threads(clo):
     ctx.close()
 
 
+def test_topk_objects_on_distinct_threads(clo):
+    """Five threads in one process: a "smallest, sorted" top-k in arg form below the cap and a "largest, input" one with
+    values (a workspace of digit tables, states and counts each, filled and read by up to twelve launches per call) next
+    to a select, one satradix sorter and one scanner."""
+    import test_gpu_by_key_queues as K
+    ctx = clo.Context(0)
+    errors = []
+    workers = [threading.Thread(target=_by_key_worker, args=(clo, ctx, kind, 70 + i, 16, 21, errors))
+               for i, kind in enumerate((K._TopKSortedArg, K._TopK, K._Select))]
+    workers += [threading.Thread(target=_sort_worker, args=(clo, ctx, "satradix", "uint", 76, 16, 21, errors)),
+                threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "ulong", 77, 16, 21, errors))]
+    assert len(workers) == 5
+    for w in workers:
+        w.start()
+    for w in workers:
+        w.join(timeout=600)
+    assert not any(w.is_alive() for w in workers), "a worker is stuck"
+    assert errors == []
+    ctx.close()
+
+
 def test_sorters_built_by_the_runtime_compiler_side_by_side(clo):
     """Two threads construct sorters through hiprtc at once (different key expressions) and sort with them."""
     ctx = clo.Context(0)
@@ -295,6 +316,12 @@ def test_search_setop_and_select_objects_give_their_device_memory_back(clo):
     kept counts): a cached workspace each."""
     import test_gpu_by_key_queues as K
     _give_back(clo, (K._Search, K._SetOp, K._Select))
+
+
+def test_topk_objects_give_their_device_memory_back(clo):
+    """And for the two top-k objects of test_gpu_by_key_queues.py: a cached workspace each."""
+    import test_gpu_by_key_queues as K
+    _give_back(clo, (K._TopK, K._TopKSortedArg))
 
 
 def _give_back(clo, kinds):

@@ -8,7 +8,9 @@ differ in one digit only; every key type with its special values; every value fo
 element-aligned views; a tile count that sends the count scan through its loop a second time; kth_out feeding two
 CloSelect objects on the same stream; the library's own argsort; one object large, small, large; two objects on two
 streams; the host-data form; the thin ABI's status codes; clo_hip_topk captured into a linear graph and replayed after
-the keys were rewritten; a seeded fuzz; and one case with element indices above 2^31."""
+the keys were rewritten; a seeded fuzz; two cases with element indices above 2^31; and, for keys of 2, 4 and 8 bytes of
+a signed or floating kind, one tile more than the digit sweep has work-groups (clo_hip_topk_sweep_groups), every winner
+in that tile. (tests/test_gpu_fuzz.py has the stratified fuzz over every kernel instantiation.)"""
 import numpy as np
 import pytest
 
@@ -280,6 +282,36 @@ def test_the_scans_take_a_second_trip(dev):
     below = int((keys < 1000).sum())
     run_topk(dev, "smallest", "input", "uint", keys, below + n // 6, "keys", "%d tiles" % (TOPK_SCAN_TRIP + 2))
     run_topk(dev, "largest", "input", "uint", keys, int((keys > 1000).sum()) + n // 5, "arg_only", "%d tiles" % (TOPK_SCAN_TRIP + 2))
+
+
+@pytest.mark.parametrize("kt", ["ushort", "half", "int", "float", "long", "double"])
+def test_the_digit_sweep_takes_a_second_trip(dev, kt):
+    """The digit sweep launches G = clo_hip_topk_sweep_groups() work-groups at most, and a group adds the tiles blockIdx.x,
+    blockIdx.x + G, ... into its LDS counters. n = (G + 1) Td + 5 (Td: the sweep's tile): tile G and the five elements
+    behind it are the second trip of groups 0 and 1. The keys come from 300 distinct values in the library's order: the
+    middle 100 before index G Td, the lowest 100 and the highest 100 mixed behind it, so that the k smallest and the k
+    largest all lie in the second trip. A sweep that stops after its first trip counts none of them, and the k-th key
+    and the rows come out wrong. "smallest, input" with keys_out, then "largest, sorted" in arg form below the cap."""
+    dt = np.dtype(_NP[kt])
+    G, Td = dev[0].topk_sweep_groups(), tile_of(dev, kt, "keys")
+    assert G >= 1
+    n = (G + 1) * Td + 5
+    assert n > G * Td and -(-n // Td) == G + 2
+    rng = np.random.default_rng(dt.itemsize * 7 + len(kt))
+    words = np.unique(rng.integers(0, 1 << (8 * dt.itemsize - 1), 400, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, 400, dtype=np.uint64))
+    pool = sort_keys(rng.permutation(words.astype("u%d" % dt.itemsize))[:300].view(dt))
+    assert pool.size == 300
+    keys = np.empty(n, dt)
+    keys[:G * Td] = pool[rng.integers(100, 200, G * Td)]
+    ends = rng.integers(0, 200, n - G * Td)
+    keys[G * Td:] = pool[np.where(ends < 100, ends, ends + 100)]
+    nlow, nhigh = int((ends < 100).sum()), int((ends >= 100).sum())
+    k1, k2 = nlow // 2, min(cap_of(dev, kt, "arg"), 2 * nhigh // 3)
+    assert 0 < k1 < nlow and 0 < k2 < nhigh
+    p, _ = run_topk(dev, "smallest", "input", kt, keys, k1, "keys", "every winner in the sweep's second trip")
+    assert p.size == k1 and int(p.min()) >= G * Td
+    p, _ = run_topk(dev, "largest", "sorted", kt, keys, k2, "arg", "every winner in the sweep's second trip")
+    assert p.size == k2 and int(p.min()) >= G * Td
 
 
 def test_kth_out_feeds_two_selects(dev):
@@ -626,4 +658,58 @@ def test_indices_above_2p31(dev):
         for x in bufs + [s]:
             x.close()
         del keys, out
+        torch.cuda.empty_cache()
+
+
+def test_indices_above_2p31_largest_with_keys_out(dev):
+    """The sibling in the other direction and with keys_out: numel = 2^31 + T + 5 ushort keys, the 1000 largest in input
+    order with their indices. The losers are below 1000; about 1200 winners (60000 .. 60009, so that the cut falls
+    inside a tie run) are planted at places that include the first element, both sides of index 2^31 and the last
+    element, those four with the largest value, so that they are chosen. keys_out's row offsets pass 2^31 elements of input, the compacted rows come from tiles on both sides.
+    The expected rows are computed from the planted places alone. (The keys are held as torch.int16: the bits count.)"""
+    import torch
+    clo, ctx, q = dev
+    T = tile_of(dev, "ushort", "arg")
+    n, k = (1 << 31) + T + 5, 1000
+    free = torch.cuda.mem_get_info()[0]
+    if free < (10 << 30):
+        pytest.skip("needs about 8 GiB of free device memory (4 GiB of keys, torch's scratch), %.1f GiB are free" % (free / 2 ** 30))
+    g = torch.Generator(device="cuda").manual_seed(32)
+    keys = torch.empty(n, dtype=torch.int16, device="cuda").random_(0, 1000, generator=g)
+    near = torch.arange(-40, 40, dtype=torch.int64, device="cuda") * 3 + (1 << 31)
+    planted = torch.cat((torch.randint(0, n, (1100,), dtype=torch.int64, device="cuda", generator=g), near,
+                         torch.tensor([0, (1 << 31) - 1, 1 << 31, n - 1], dtype=torch.int64, device="cuda")))
+    planted = torch.unique(planted)
+    ends = torch.tensor([0, (1 << 31) - 1, 1 << 31, n - 1], dtype=torch.int64, device="cuda")
+    value = torch.where(torch.isin(planted, ends), 60009, 60000 + (planted * 7 + planted // 1000) % 10)   # the four ends are chosen
+    keys[planted] = (value - 65536).to(torch.int16)                                                     # the bits of 60000 .. 60009
+    rows = torch.full((k + 16,), -0x3C3C3C3D, dtype=torch.int32, device="cuda")                         # bytes C3 C3 C3 C3
+    kout = torch.full((k + 16,), -0x3C3D, dtype=torch.int16, device="cuda")
+    kth = torch.full((4,), -0x3C3D, dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    pos, val = planted.cpu().numpy(), value.cpu().numpy()
+    assert pos.size > k
+    chosen = np.lexsort((pos, -val))[:k]                                                                # the largest first, ties by index
+    cut = int(val[chosen[-1]])
+    assert int((val[chosen] == cut).sum()) < int((val == cut).sum())                                    # the cut falls inside a tie run
+    in_order = np.sort(chosen)                                                                          # (pos is ascending)
+    want, want_keys = pos[in_order], val[in_order].astype(np.uint16)
+    assert want[0] == 0 and want[-1] == n - 1 and {(1 << 31) - 1, 1 << 31} <= set(want.tolist())
+    bufs = [clo.Buffer(ctx, 2 * n, device_ptr=keys.data_ptr()), clo.Buffer(ctx, 2 * k, device_ptr=kout.data_ptr()),
+            clo.Buffer(ctx, 4 * k, device_ptr=rows.data_ptr()), clo.Buffer(ctx, 2, device_ptr=kth.data_ptr())]
+    s = clo.TopK("largest", "input", ctx, "ushort", 4)
+    try:
+        assert s.with_device_data(q, bufs[0], None, bufs[1], bufs[2], bufs[3], n, k)
+        q.finish()
+        got = rows[:k].to(torch.int64).cpu().numpy() & 0xFFFFFFFF                                       # the indices are uint
+        got_keys, got_kth = kout.cpu().numpy().view(np.uint16), kth.cpu().numpy().view(np.uint16)
+        assert np.array_equal(got, want), "the indices differ from the planted winners"
+        assert np.array_equal(got_keys[:k], want_keys), "keys_out differs from the planted winners"
+        assert int(got_kth[0]) == cut and bool((got_kth[1:] == 0xC3C3).all())
+        assert bool((got_keys[k:] == 0xC3C3).all()) and bool((rows[k:] == -0x3C3C3C3D).all().item()), "rows >= k were written"
+        assert keys[planted].to(torch.int64).cpu().numpy().tolist() == (val - 65536).tolist() and int(keys.max()) < 1000, "keys_in changed"
+    finally:
+        for x in bufs + [s]:
+            x.close()
+        del keys, rows, kout
         torch.cuda.empty_cache()

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PUBLIC = ("clo_topk_new", "clo_topk_destroy", "clo_topk_with_device_data", "clo_topk_with_host_data",
           "clo_topk_get_context", "clo_topk_get_key_type", "clo_topk_get_key_size", "clo_topk_get_value_size",
           "clo_topk_get_which", "clo_topk_get_order")
-THIN = ("clo_hip_topk", "clo_hip_topk_workspace_bytes", "clo_hip_topk_tile", "clo_hip_topk_sorted_max")
+THIN = ("clo_hip_topk", "clo_hip_topk_workspace_bytes", "clo_hip_topk_tile", "clo_hip_topk_sweep_groups", "clo_hip_topk_sorted_max")
 
 
 def test_exports():
@@ -50,7 +50,7 @@ def test_exports():
         assert "#define CLO_HIP_TOPK_%s %d\n" % (n.upper().ljust(6), i) in text, n
     assert "#define CLO_HIP_TOPK_SCAN_TRIP %d\n" % TOPK_SCAN_TRIP in text
     assert '#include "clo_topk.h"' in open(os.path.join(ROOT, "include", "cl_ops.h")).read()
-    for n in ("TopK", "topk_tile", "topk_sorted_max", "TOPK_WHICH", "TOPK_ORDERS"):
+    for n in ("TopK", "topk_tile", "topk_sweep_groups", "topk_sorted_max", "TOPK_WHICH", "TOPK_ORDERS"):
         assert getattr(clo, n) is not None and n in clo.__all__
 
 
