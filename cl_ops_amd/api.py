@@ -205,6 +205,52 @@ def _b(s):
     return None if s is None else s.encode()
 
 
+def _h(obj):
+    """The C handle of a wrapper object; None (NULL) for None."""
+    return obj.h if obj is not None else None
+
+
+def _p(array):
+    """The data pointer of a numpy array; None (NULL) for None."""
+    return array.ctypes.data_as(vp) if array is not None else None
+
+
+def _keys_1d(arr, key_size, what):
+    """arr as a contiguous 1-D array of key_size-byte elements."""
+    k = np.ascontiguousarray(arr)
+    if k.ndim != 1 or k.itemsize != key_size:
+        raise ValueError("%s: a 1-D array of %d-byte elements" % (what, key_size))
+    return k
+
+
+def _values_like(values, keys, value_size, what):
+    """values (or None) as a contiguous array of value_size-byte elements, one per key."""
+    if values is None:
+        return None
+    v = np.ascontiguousarray(values)
+    if v.shape != keys.shape or v.itemsize != value_size or value_size == 0:
+        raise ValueError("%s: %d-byte elements, as many as keys" % (what, value_size))
+    return v
+
+
+class _Handle:
+    """A C object behind a ctypes handle: made by a clo_*_new (whose NULL without an error is an error too), ended by
+    close()."""
+    _destroy = None   # the name of its clo_*_destroy
+
+    def _new(self, new, *args):
+        err = _Err()
+        self.h = getattr(lib, new)(*args, err.ref)
+        err.raise_if_set()
+        if not self.h:
+            raise CloError("clo", CLO_ERROR_LIBRARY, new + " returned NULL")
+
+    def close(self):
+        if self.h:
+            getattr(lib, self._destroy)(self.h)
+            self.h = None
+
+
 def clo_type(t):
     """CloType constant from a name ('uint'), a numpy dtype, or an int."""
     if isinstance(t, int):
@@ -377,9 +423,8 @@ class Sorter:
         """clo_sort_by_key_with_device_data: stable sort of keys_in carrying 4-byte values along (satradix).
         values_in None: the values are the indices 0 .. numel - 1 (argsort); keys_out None: no keys are written."""
         err = _Err()
-        h = lambda b: b.h if b is not None else None
-        evt = lib.clo_sort_by_key_with_device_data(self.h, q_exec.h, h(q_comm), h(keys_in), h(values_in), h(keys_out),
-                                                   h(values_out), numel, lws_max, err.ref)
+        evt = lib.clo_sort_by_key_with_device_data(self.h, q_exec.h, _h(q_comm), _h(keys_in), _h(values_in), _h(keys_out),
+                                                   _h(values_out), numel, lws_max, err.ref)
         err.raise_if_set()
         return evt
 

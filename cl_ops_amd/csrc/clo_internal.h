@@ -184,4 +184,68 @@ CLO_INTERNAL int clo_hip_failed(int st, GError** err, const char* what);
 typedef int (*clo_option_cb)(const char* key, const char* value, const char* token, void* user, GError** err);
 CLO_INTERNAL int clo_parse_options(const char* options, clo_option_cb cb, void* user, const char* algo, GError** err);
 
+/* ---- The host layer the operation drivers share (clo_op_host.c): clo_histogram.c, clo_reduce_by_key.c,
+ * clo_scan_by_key.c, clo_merge.c, clo_search.c, clo_setop.c, clo_select.c and clo_topk.c keep only what is particular
+ * to their operation (options, refusals and their wording, size tables, the one thin-ABI call, getters). ---- */
+
+/* 0 unsigned, 1 signed, 2 IEEE total order: the key kinds of clo_sort_by_key_* */
+CLO_INTERNAL int clo_type_key_kind(CloType t);
+/* int, uint, long or ulong: the value and sum types of the aggregating operations */
+CLO_INTERNAL int clo_type_is_int32_or_64(CloType t);
+/* The position of name among names[0 .. count), or -1 (for NULL too). */
+CLO_INTERNAL int clo_name_index(const char* name, const char* const* names, int count);
+
+/* A range of addresses, of the device or of the host: nothing is dereferenced. A NULL or empty range overlaps nothing. */
+typedef struct { const void* p; size_t bytes; } clo_range;
+CLO_INTERNAL int clo_ranges_overlap(clo_range a, clo_range b);
+/* 0, or why the outputs cannot be written: output by output, CLO_RANGES_OUT_IN when it overlaps an input, else
+ * CLO_RANGES_OUT_OUT when it overlaps an earlier output. */
+enum { CLO_RANGES_OUT_IN = 1, CLO_RANGES_OUT_OUT = 2 };
+CLO_INTERNAL int clo_ranges_conflict(const clo_range* in, int nin, const clo_range* out, int nout);
+
+/* What every operation object starts with (its FIRST member, so that the object's address is the head's). */
+typedef struct {
+	CCLContext* ctx;
+	clo_devbuf workspace;    /* what the operation's clo_hip_*_workspace_bytes asks for; grows, never shrinks */
+	clo_stream_guard guard;  /* the workspace belongs to one queue at a time */
+} clo_op_head;
+/* A zeroed object of `size` bytes holding a reference to ctx, or NULL with CLO_ERROR_LIBRARY; and its end. */
+CLO_INTERNAL void* clo_op_new(size_t size, CCLContext* ctx, GError** err);
+CLO_INTERNAL void clo_op_destroy(void* op);
+/* Before a call on cq that needs ws bytes of workspace: orders the call after the workspace's last user, grows the
+ * workspace. `what` names the allocation in the error. 1, or 0 with *err set. */
+CLO_INTERNAL int clo_op_reserve(clo_op_head* op, CCLQueue* cq, size_t ws, const char* what, GError** err);
+
+/* p[i]: the device pointer of buf[i], NULL for NULL. */
+CLO_INTERNAL void clo_buffers_device_ptrs(CCLBuffer* const* buf, void** p, int n);
+/* 1 if every buffer that is not NULL holds need[i] bytes. */
+CLO_INTERNAL int clo_buffers_hold(CCLBuffer* const* buf, const size_t* need, int n);
+/* Closes the command evt of cq (ccl_queue_begin_command) around the thin-ABI call `what` that returned st: the event,
+ * or NULL with *err set and the command taken back. */
+CLO_INTERNAL CCLEvent* clo_op_end_command(CCLQueue* cq, CCLEvent* evt, int st, const char* what, GError** err);
+
+/* The device side of a *_with_host_data call: a queue of its own when the caller gave none, one device buffer per
+ * slot, blocking transfers on cq_comm. The first failure is kept in `err` and every later step does nothing, so a
+ * driver writes the steps one after the other and asks once, at clo_stage_close. In between it makes its device call
+ * itself: `if (clo_stage_ok(&st)) st.evt = clo_x_with_device_data(..., st.cq_exec, st.cq_comm, st.dev[..], &st.err);`
+ * — the first read-back then waits for st.evt. A slot whose host pointer is NULL or that holds 0 bytes stays NULL. */
+#define CLO_STAGE_SLOTS 8
+typedef struct {
+	CCLContext* ctx;
+	CCLQueue* cq_exec;
+	CCLQueue* cq_comm;
+	CCLQueue* own_queue;     /* made here because the caller passed no cq_exec; destroyed by clo_stage_close */
+	CCLBuffer* dev[CLO_STAGE_SLOTS];
+	CCLEvent* evt;           /* the device call's event, until the first read has waited for it */
+	CCLEventWaitList ewl;
+	GError* err;
+} clo_stage;
+CLO_INTERNAL void clo_stage_open(clo_stage* st, CCLContext* ctx, CCLQueue* cq_exec, CCLQueue* cq_comm);
+#define clo_stage_ok(st) ((st)->err == NULL)
+CLO_INTERNAL void clo_stage_in(clo_stage* st, int slot, const void* host, size_t bytes);    /* allocates and uploads */
+CLO_INTERNAL void clo_stage_out(clo_stage* st, int slot, const void* host, size_t bytes);   /* allocates */
+CLO_INTERNAL void clo_stage_read(clo_stage* st, int slot, void* host, size_t bytes);        /* the first bytes of the slot */
+/* Moves the failure, if any, to *err; releases the buffers and the queue made here. CL_TRUE if nothing failed. */
+CLO_INTERNAL cl_bool clo_stage_close(clo_stage* st, GError** err);
+
 #endif

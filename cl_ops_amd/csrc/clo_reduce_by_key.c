@@ -1,6 +1,7 @@
 /*
  * clo_reduce_by_key.c — CloReduceByKey (include/clo_reduce.h; not upstream): every run of equal keys collapsed
- * into one row. The kernels are reached through the thin C-ABI (clo_hip_reduce_by_key, include/clo_hip.h).
+ * into one row. The kernels are reached through the thin C-ABI (clo_hip_reduce_by_key, include/clo_hip.h); the host
+ * layer is the one the operation drivers share (clo_internal.h).
  *
  * Every argument is checked before anything touches the device, so that the refusals come back the same on a
  * context without one. err may be NULL everywhere.
@@ -8,7 +9,6 @@
 #include "clo_reduce.h"
 
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "clo_internal.h"
@@ -16,23 +16,17 @@
 #define CLO_REDUCE_BY_KEY_EVENT "clo_reduce_by_key"
 
 struct clo_reduce_by_key {
-	CCLContext* ctx;
+	clo_op_head head;        /* the workspace: the tile states */
 	CloType key_type, value_type, sum_type;
 	int op;                  /* index in rbk_ops: what clo_hip_reduce_by_key takes */
-	clo_devbuf workspace;    /* the tile states; grows, never shrinks */
-	clo_stream_guard guard;  /* the workspace belongs to one queue at a time */
 };
 
 static const char* const rbk_ops[] = { "sum", "min", "max" };
 
-static int rbk_value_type_ok(CloType t) { return t == CLO_INT || t == CLO_UINT || t == CLO_LONG || t == CLO_ULONG; }
-
 CloReduceByKey* clo_reduce_by_key_new(const char* op, const char* options, CCLContext* ctx,
 	CloType key_type, CloType value_type, CloType sum_type, GError** err) {
 	clo_return_val_if_fail(err == NULL || *err == NULL, NULL);
-	int opi = -1;
-	for (int i = 0; op && i < 3; ++i)
-		if (!strcmp(op, rbk_ops[i])) opi = i;
+	const int opi = clo_name_index(op, rbk_ops, 3);
 	if (opi < 0) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "Unknown reduce-by-key operation '%s' (one of: " CLO_REDUCE_BY_KEY_OPS ").",
 			op ? op : "(null)");
@@ -50,7 +44,7 @@ CloReduceByKey* clo_reduce_by_key_new(const char* op, const char* options, CCLCo
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "Unknown key type %d.", (int) key_type);
 		return NULL;
 	}
-	if (!rbk_value_type_ok(value_type) || !rbk_value_type_ok(sum_type)) {
+	if (!clo_type_is_int32_or_64(value_type) || !clo_type_is_int32_or_64(sum_type)) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "Reduce by key takes values and sums of type int, uint, long or ulong "
 			"(floating-point aggregates depend on the order of addition; narrower values are not built), not '%s' into '%s'.",
 			clo_type_get_name(value_type) ? clo_type_get_name(value_type) : "?", clo_type_get_name(sum_type) ? clo_type_get_name(sum_type) : "?");
@@ -61,13 +55,8 @@ CloReduceByKey* clo_reduce_by_key_new(const char* op, const char* options, CCLCo
 			clo_type_get_name(sum_type), clo_type_get_name(value_type));
 		return NULL;
 	}
-	CloReduceByKey* rbk = (CloReduceByKey*) calloc(1, sizeof(CloReduceByKey));
-	if (!rbk) {
-		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_LIBRARY, "Out of host memory.");
-		return NULL;
-	}
-	ccl_context_ref(ctx);
-	rbk->ctx = ctx;
+	CloReduceByKey* rbk = (CloReduceByKey*) clo_op_new(sizeof(CloReduceByKey), ctx, err);
+	if (!rbk) return NULL;
 	rbk->key_type = key_type;
 	rbk->value_type = value_type;
 	rbk->sum_type = sum_type;
@@ -77,16 +66,7 @@ CloReduceByKey* clo_reduce_by_key_new(const char* op, const char* options, CCLCo
 
 void clo_reduce_by_key_destroy(CloReduceByKey* rbk) {
 	clo_return_if_fail(rbk != NULL);
-	clo_devbuf_release(&rbk->workspace);
-	clo_stream_guard_release(&rbk->guard);
-	ccl_context_unref(rbk->ctx);
-	free(rbk);
-}
-
-static int rbk_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-	if (!a || !b || !abytes || !bbytes) return 0;
-	const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-	return a0 < b0 + bbytes && b0 < a0 + abytes;
+	clo_op_destroy(rbk);
 }
 
 /* Why these arguments are refused, or NULL; pointers of the device or of the host, nothing is dereferenced.
@@ -100,17 +80,13 @@ static const char* rbk_refusal(CloReduceByKey* rbk, const void* keys_in, const v
 	if (numel > 0 && !keys_in) return "keys_in is required";
 	const size_t kb = numel * clo_type_sizeof(rbk->key_type), vb = numel * clo_type_sizeof(rbk->value_type),
 		sb = numel * clo_type_sizeof(rbk->sum_type);
-	const void* in[2] = { keys_in, values_in };
-	const size_t inb[2] = { kb, vb };
-	const void* out[3] = { keys_out, aggr_out, count };
-	const size_t outb[3] = { kb, sb, sizeof(cl_ulong) };
-	for (int o = 0; o < 3; ++o) {
-		for (int i = 0; i < 2; ++i)
-			if (rbk_overlap(out[o], outb[o], in[i], inb[i]))
-				return "an output range overlaps an input range (rows land below the elements they come from, in tiles that "
-					"may not have been read yet: reduce by key does not work in place)";
-		for (int p = 0; p < o; ++p)
-			if (rbk_overlap(out[o], outb[o], out[p], outb[p])) return "two output ranges overlap";
+	const clo_range in[2] = { { keys_in, kb }, { values_in, vb } };
+	const clo_range out[3] = { { keys_out, kb }, { aggr_out, sb }, { count, sizeof(cl_ulong) } };
+	switch (clo_ranges_conflict(in, 2, out, 3)) {
+		case CLO_RANGES_OUT_IN:
+			return "an output range overlaps an input range (rows land below the elements they come from, in tiles that "
+				"may not have been read yet: reduce by key does not work in place)";
+		case CLO_RANGES_OUT_OUT: return "two output ranges overlap";
 	}
 	return NULL;
 }
@@ -121,22 +97,19 @@ CCLEvent* clo_reduce_by_key_with_device_data(CloReduceByKey* rbk, CCLQueue* cq_e
 	clo_return_val_if_fail(rbk != NULL, NULL);
 	clo_return_val_if_fail(err == NULL || *err == NULL, NULL);
 	(void) cq_comm;   /* nothing is copied */
-	void* kin = keys_in ? ccl_buffer_get_device_ptr(keys_in) : NULL;
-	void* vin = values_in ? ccl_buffer_get_device_ptr(values_in) : NULL;
-	void* kout = keys_out ? ccl_buffer_get_device_ptr(keys_out) : NULL;
-	void* aout = aggr_out ? ccl_buffer_get_device_ptr(aggr_out) : NULL;
-	void* count = num_runs_out ? ccl_buffer_get_device_ptr(num_runs_out) : NULL;
-	const char* why = rbk_refusal(rbk, kin, vin, kout, aout, count, numel);
-	if (!why && ((uintptr_t) count & 7u)) why = "the run count must be 8-byte aligned";
+	CCLBuffer* const buf[5] = { keys_in, values_in, keys_out, aggr_out, num_runs_out };
+	void* p[5];
+	clo_buffers_device_ptrs(buf, p, 5);
+	const char* why = rbk_refusal(rbk, p[0], p[1], p[2], p[3], p[4], numel);
+	if (!why && ((uintptr_t) p[4] & 7u)) why = "the run count must be 8-byte aligned";
 	if (why) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "%s", why);
 		return NULL;
 	}
 	const size_t kb = numel * clo_type_sizeof(rbk->key_type), vb = numel * clo_type_sizeof(rbk->value_type),
 		sb = numel * clo_type_sizeof(rbk->sum_type);
-	if ((keys_in && kb > ccl_buffer_get_size(keys_in)) || (values_in && vb > ccl_buffer_get_size(values_in))
-		|| (keys_out && kb > ccl_buffer_get_size(keys_out)) || (aggr_out && sb > ccl_buffer_get_size(aggr_out))
-		|| ccl_buffer_get_size(num_runs_out) < sizeof(cl_ulong)) {
+	const size_t need[5] = { kb, vb, kb, sb, sizeof(cl_ulong) };
+	if (!clo_buffers_hold(buf, need, 5)) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "numel (%zu) exceeds the size of the device buffers", numel);
 		return NULL;
 	}
@@ -145,18 +118,13 @@ CCLEvent* clo_reduce_by_key_with_device_data(CloReduceByKey* rbk, CCLQueue* cq_e
 		clo_type_get_name(rbk->key_type), values_in ? clo_type_get_name(rbk->value_type) : "absent",
 		aggr_out ? clo_type_get_name(rbk->sum_type) : "not written", keys_out ? "written" : "not written");
 
-	if (numel > 0) {
-		if (clo_hip_failed(clo_stream_guard_enter(&rbk->guard, cq_exec), err, "hipStreamWaitEvent")) return NULL;
-		if (clo_hip_failed(clo_devbuf_reserve(&rbk->workspace, clo_hip_reduce_by_key_workspace_bytes(numel)), err,
-			"hipMalloc(reduce-by-key workspace)")) return NULL;
-	}
+	if (numel > 0 && !clo_op_reserve(&rbk->head, cq_exec, clo_hip_reduce_by_key_workspace_bytes(numel), "hipMalloc(reduce-by-key workspace)", err))
+		return NULL;
 	CCLEvent* evt = ccl_queue_begin_command(cq_exec, CLO_REDUCE_BY_KEY_EVENT, err);
 	if (!evt) return NULL;
-	const int st = clo_hip_reduce_by_key(kin, vin, kout, aout, (uint64_t*) count, numel, (int) clo_type_sizeof(rbk->key_type),
-		(int) rbk->value_type, (int) rbk->sum_type, rbk->op, rbk->workspace.ptr, rbk->workspace.bytes, ccl_queue_get_stream(cq_exec));
-	if (clo_hip_failed(st, err, "clo_hip_reduce_by_key")) { ccl_queue_abort_command(cq_exec, evt); return NULL; }
-	if (!ccl_queue_end_command(cq_exec, evt, err)) { ccl_queue_abort_command(cq_exec, evt); return NULL; }
-	return evt;
+	const int st = clo_hip_reduce_by_key(p[0], p[1], p[2], p[3], (uint64_t*) p[4], numel, (int) clo_type_sizeof(rbk->key_type),
+		(int) rbk->value_type, (int) rbk->sum_type, rbk->op, rbk->head.workspace.ptr, rbk->head.workspace.bytes, ccl_queue_get_stream(cq_exec));
+	return clo_op_end_command(cq_exec, evt, st, "clo_hip_reduce_by_key", err);
 }
 
 cl_bool clo_reduce_by_key_with_host_data(CloReduceByKey* rbk, CCLQueue* cq_exec, CCLQueue* cq_comm,
@@ -172,72 +140,31 @@ cl_bool clo_reduce_by_key_with_host_data(CloReduceByKey* rbk, CCLQueue* cq_exec,
 	*num_runs = 0;
 	if (numel == 0) return CL_TRUE;
 
-	cl_bool status = CL_FALSE;
-	CCLBuffer* dev[5] = { NULL, NULL, NULL, NULL, NULL };   /* keys in, values in, keys out, aggregates out, run count */
-	CCLQueue* intern_queue = NULL;
-	CCLEvent* evt = NULL;
-	CCLEventWaitList ewl = NULL;
-	GError* err_internal = NULL;
 	const size_t ks = clo_type_sizeof(rbk->key_type), vs = clo_type_sizeof(rbk->value_type), ss = clo_type_sizeof(rbk->sum_type);
-	const size_t bytes[5] = { numel * ks, numel * vs, numel * ks, numel * ss, sizeof(cl_ulong) };
-	const int used[5] = { 1, values_in != NULL, keys_out != NULL, aggr_out != NULL, 1 };
 	cl_ulong m = 0;
-	CCLContext* ctx = rbk->ctx;
-
-	if (cq_exec == NULL) {
-		CCLDevice* d = ccl_context_get_device(ctx, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		intern_queue = ccl_queue_new(ctx, d, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		cq_exec = intern_queue;
-	}
-	if (cq_comm == NULL) cq_comm = cq_exec;
-	for (int i = 0; i < 5; ++i) {
-		if (!used[i]) continue;
-		dev[i] = ccl_buffer_new(ctx, CL_MEM_READ_WRITE, bytes[i], NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	ccl_buffer_enqueue_write(dev[0], cq_comm, CL_TRUE, 0, bytes[0], (void*) keys_in, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	if (values_in) {
-		ccl_buffer_enqueue_write(dev[1], cq_comm, CL_TRUE, 0, bytes[1], (void*) values_in, NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	evt = clo_reduce_by_key_with_device_data(rbk, cq_exec, cq_comm, dev[0], dev[1], dev[2], dev[3], dev[4], numel, &err_internal);
-	if (err_internal) goto error_handler;
+	/* keys in, values in, keys out, aggregates out, run count */
+	clo_stage st;
+	clo_stage_open(&st, rbk->head.ctx, cq_exec, cq_comm);
+	clo_stage_in(&st, 0, keys_in, numel * ks);
+	clo_stage_in(&st, 1, values_in, numel * vs);
+	clo_stage_out(&st, 2, keys_out, numel * ks);
+	clo_stage_out(&st, 3, aggr_out, numel * ss);
+	clo_stage_out(&st, 4, num_runs, sizeof(cl_ulong));
+	if (clo_stage_ok(&st))
+		st.evt = clo_reduce_by_key_with_device_data(rbk, st.cq_exec, st.cq_comm, st.dev[0], st.dev[1], st.dev[2], st.dev[3], st.dev[4], numel, &st.err);
 	/* the run count first (blocking): it says how many rows there are to copy */
-	ccl_buffer_enqueue_read(dev[4], cq_comm, CL_TRUE, 0, sizeof(cl_ulong), &m, evt ? ccl_ewl(&ewl, evt, NULL) : NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	if (m > numel) {
-		clo_gerror_set(&err_internal, CLO_ERROR, CLO_ERROR_LIBRARY, "reduce by key: %llu runs of %zu elements", (unsigned long long) m, numel);
-		goto error_handler;
-	}
-	if (keys_out) {
-		ccl_buffer_enqueue_read(dev[2], cq_comm, CL_TRUE, 0, (size_t) m * ks, keys_out, NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	if (aggr_out) {
-		ccl_buffer_enqueue_read(dev[3], cq_comm, CL_TRUE, 0, (size_t) m * ss, aggr_out, NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	*num_runs = (size_t) m;
-	status = CL_TRUE;
-	goto finish;
-
-error_handler:
-	clo_gerror_propagate(err, err_internal);
-	status = CL_FALSE;
-
-finish:
-	ccl_event_wait_list_clear(&ewl);
-	for (int i = 0; i < 5; ++i) if (dev[i]) ccl_buffer_destroy(dev[i]);
-	if (intern_queue) ccl_queue_destroy(intern_queue);
-	return status;
+	clo_stage_read(&st, 4, &m, sizeof(cl_ulong));
+	if (clo_stage_ok(&st) && m > numel)
+		clo_gerror_set(&st.err, CLO_ERROR, CLO_ERROR_LIBRARY, "reduce by key: %llu runs of %zu elements", (unsigned long long) m, numel);
+	clo_stage_read(&st, 2, keys_out, (size_t) m * ks);
+	clo_stage_read(&st, 3, aggr_out, (size_t) m * ss);
+	if (clo_stage_ok(&st)) *num_runs = (size_t) m;
+	return clo_stage_close(&st, err);
 }
 
 CCLContext* clo_reduce_by_key_get_context(CloReduceByKey* rbk) {
 	clo_return_val_if_fail(rbk != NULL, NULL);
-	return rbk->ctx;
+	return rbk->head.ctx;
 }
 
 CloType clo_reduce_by_key_get_key_type(CloReduceByKey* rbk) {

@@ -1,7 +1,7 @@
 /*
  * clo_scan_by_key.c — CloScanByKey (include/clo_scan_by_key.h; not upstream): the running sum / min / max of every
  * element within its run of equal keys. The kernels are reached through the thin C-ABI (clo_hip_scan_by_key,
- * include/clo_hip.h). Follows clo_reduce_by_key.c point for point.
+ * include/clo_hip.h); the host layer is the one the operation drivers share (clo_internal.h).
  *
  * Every argument is checked before anything touches the device, so that the refusals come back the same on a
  * context without one. err may be NULL everywhere.
@@ -9,7 +9,6 @@
 #include "clo_scan_by_key.h"
 
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "clo_internal.h"
@@ -17,17 +16,13 @@
 #define CLO_SCAN_BY_KEY_EVENT "clo_scan_by_key"
 
 struct clo_scan_by_key {
-	CCLContext* ctx;
+	clo_op_head head;        /* the workspace: the tile states */
 	CloType key_type, value_type, sum_type;
 	int op;                  /* index in sbk_ops: what clo_hip_scan_by_key takes */
 	int inclusive;           /* 0 or 1 */
-	clo_devbuf workspace;    /* the tile states; grows, never shrinks */
-	clo_stream_guard guard;  /* the workspace belongs to one queue at a time */
 };
 
 static const char* const sbk_ops[] = { "sum", "min", "max" };
-
-static int sbk_value_type_ok(CloType t) { return t == CLO_INT || t == CLO_UINT || t == CLO_LONG || t == CLO_ULONG; }
 
 /* the one option there is: inclusive=0 | inclusive=1 */
 static int sbk_option(const char* key, const char* value, const char* token, void* user, GError** err) {
@@ -42,9 +37,7 @@ static int sbk_option(const char* key, const char* value, const char* token, voi
 CloScanByKey* clo_scan_by_key_new(const char* op, const char* options, CCLContext* ctx,
 	CloType key_type, CloType value_type, CloType sum_type, GError** err) {
 	clo_return_val_if_fail(err == NULL || *err == NULL, NULL);
-	int opi = -1;
-	for (int i = 0; op && i < 3; ++i)
-		if (!strcmp(op, sbk_ops[i])) opi = i;
+	const int opi = clo_name_index(op, sbk_ops, 3);
 	if (opi < 0) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "Unknown scan-by-key operation '%s' (one of: " CLO_SCAN_BY_KEY_OPS ").",
 			op ? op : "(null)");
@@ -66,7 +59,7 @@ CloScanByKey* clo_scan_by_key_new(const char* op, const char* options, CCLContex
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "Unknown key type %d.", (int) key_type);
 		return NULL;
 	}
-	if (!sbk_value_type_ok(value_type) || !sbk_value_type_ok(sum_type)) {
+	if (!clo_type_is_int32_or_64(value_type) || !clo_type_is_int32_or_64(sum_type)) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "Scan by key takes values and sums of type int, uint, long or ulong "
 			"(floating-point aggregates depend on the order of addition; narrower values are not built), not '%s' into '%s'.",
 			clo_type_get_name(value_type) ? clo_type_get_name(value_type) : "?", clo_type_get_name(sum_type) ? clo_type_get_name(sum_type) : "?");
@@ -77,13 +70,8 @@ CloScanByKey* clo_scan_by_key_new(const char* op, const char* options, CCLContex
 			clo_type_get_name(sum_type), clo_type_get_name(value_type));
 		return NULL;
 	}
-	CloScanByKey* sbk = (CloScanByKey*) calloc(1, sizeof(CloScanByKey));
-	if (!sbk) {
-		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_LIBRARY, "Out of host memory.");
-		return NULL;
-	}
-	ccl_context_ref(ctx);
-	sbk->ctx = ctx;
+	CloScanByKey* sbk = (CloScanByKey*) clo_op_new(sizeof(CloScanByKey), ctx, err);
+	if (!sbk) return NULL;
 	sbk->key_type = key_type;
 	sbk->value_type = value_type;
 	sbk->sum_type = sum_type;
@@ -94,16 +82,7 @@ CloScanByKey* clo_scan_by_key_new(const char* op, const char* options, CCLContex
 
 void clo_scan_by_key_destroy(CloScanByKey* sbk) {
 	clo_return_if_fail(sbk != NULL);
-	clo_devbuf_release(&sbk->workspace);
-	clo_stream_guard_release(&sbk->guard);
-	ccl_context_unref(sbk->ctx);
-	free(sbk);
-}
-
-static int sbk_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-	if (!a || !b || !abytes || !bbytes) return 0;
-	const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-	return a0 < b0 + bbytes && b0 < a0 + abytes;
+	clo_op_destroy(sbk);
 }
 
 /* Why these arguments are refused, or NULL; pointers of the device or of the host, nothing is dereferenced. */
@@ -113,12 +92,12 @@ static const char* sbk_refusal(CloScanByKey* sbk, const void* keys_in, const voi
 	if (numel == 0) return NULL;
 	if (!keys_in) return "keys_in is required";
 	if (!data_out) return "data_out is required";
-	const size_t kb = numel * clo_type_sizeof(sbk->key_type), vb = numel * clo_type_sizeof(sbk->value_type),
-		sb = numel * clo_type_sizeof(sbk->sum_type);
-	if (sbk_overlap(data_out, sb, keys_in, kb))
+	const clo_range keys = { keys_in, numel * clo_type_sizeof(sbk->key_type) }, values = { values_in, numel * clo_type_sizeof(sbk->value_type) },
+		out = { data_out, numel * clo_type_sizeof(sbk->sum_type) };
+	if (clo_ranges_overlap(out, keys))
 		return "data_out overlaps keys_in (the apply sweep reads the key to the left of its tile, which another work-group "
 			"must not have overwritten)";
-	if (sbk_overlap(data_out, sb, values_in, vb) && !(data_out == values_in && sb == vb))
+	if (clo_ranges_overlap(out, values) && !(data_out == values_in && out.bytes == values.bytes))
 		return "data_out overlaps values_in without being exactly it with a sum type as wide as the value type (in place "
 			"works only where element i's result lands on element i's value)";
 	return NULL;
@@ -129,39 +108,32 @@ CCLEvent* clo_scan_by_key_with_device_data(CloScanByKey* sbk, CCLQueue* cq_exec,
 	clo_return_val_if_fail(sbk != NULL, NULL);
 	clo_return_val_if_fail(err == NULL || *err == NULL, NULL);
 	(void) cq_comm;   /* nothing is copied */
-	void* kin = keys_in ? ccl_buffer_get_device_ptr(keys_in) : NULL;
-	void* vin = values_in ? ccl_buffer_get_device_ptr(values_in) : NULL;
-	void* out = data_out ? ccl_buffer_get_device_ptr(data_out) : NULL;
-	const char* why = sbk_refusal(sbk, kin, vin, out, numel);
+	CCLBuffer* const buf[3] = { keys_in, values_in, data_out };
+	void* p[3];
+	clo_buffers_device_ptrs(buf, p, 3);
+	const char* why = sbk_refusal(sbk, p[0], p[1], p[2], numel);
 	if (why) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "%s", why);
 		return NULL;
 	}
-	const size_t kb = numel * clo_type_sizeof(sbk->key_type), vb = numel * clo_type_sizeof(sbk->value_type),
-		sb = numel * clo_type_sizeof(sbk->sum_type);
-	if ((keys_in && kb > ccl_buffer_get_size(keys_in)) || (values_in && vb > ccl_buffer_get_size(values_in))
-		|| (data_out && sb > ccl_buffer_get_size(data_out))) {
+	const size_t need[3] = { numel * clo_type_sizeof(sbk->key_type), numel * clo_type_sizeof(sbk->value_type), numel * clo_type_sizeof(sbk->sum_type) };
+	if (!clo_buffers_hold(buf, need, 3)) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "numel (%zu) exceeds the size of the device buffers", numel);
 		return NULL;
 	}
 	clo_return_val_if_fail(cq_exec != NULL, NULL);
 	clo_debug("SCAN BY KEY: %s %s, numel=%zu, key %s, values %s, sum %s%s", sbk->inclusive ? "inclusive" : "exclusive", sbk_ops[sbk->op], numel,
 		clo_type_get_name(sbk->key_type), values_in ? clo_type_get_name(sbk->value_type) : "absent",
-		clo_type_get_name(sbk->sum_type), (out && out == vin) ? ", in place" : "");
+		clo_type_get_name(sbk->sum_type), (p[2] && p[2] == p[1]) ? ", in place" : "");
 
-	if (numel > 0) {
-		if (clo_hip_failed(clo_stream_guard_enter(&sbk->guard, cq_exec), err, "hipStreamWaitEvent")) return NULL;
-		if (clo_hip_failed(clo_devbuf_reserve(&sbk->workspace, clo_hip_scan_by_key_workspace_bytes(numel)), err,
-			"hipMalloc(scan-by-key workspace)")) return NULL;
-	}
+	if (numel > 0 && !clo_op_reserve(&sbk->head, cq_exec, clo_hip_scan_by_key_workspace_bytes(numel), "hipMalloc(scan-by-key workspace)", err))
+		return NULL;
 	CCLEvent* evt = ccl_queue_begin_command(cq_exec, CLO_SCAN_BY_KEY_EVENT, err);
 	if (!evt) return NULL;
-	const int st = clo_hip_scan_by_key(kin, vin, out, numel, (int) clo_type_sizeof(sbk->key_type),
-		(int) sbk->value_type, (int) sbk->sum_type, sbk->op, sbk->inclusive, sbk->workspace.ptr, sbk->workspace.bytes,
+	const int st = clo_hip_scan_by_key(p[0], p[1], p[2], numel, (int) clo_type_sizeof(sbk->key_type),
+		(int) sbk->value_type, (int) sbk->sum_type, sbk->op, sbk->inclusive, sbk->head.workspace.ptr, sbk->head.workspace.bytes,
 		ccl_queue_get_stream(cq_exec));
-	if (clo_hip_failed(st, err, "clo_hip_scan_by_key")) { ccl_queue_abort_command(cq_exec, evt); return NULL; }
-	if (!ccl_queue_end_command(cq_exec, evt, err)) { ccl_queue_abort_command(cq_exec, evt); return NULL; }
-	return evt;
+	return clo_op_end_command(cq_exec, evt, st, "clo_hip_scan_by_key", err);
 }
 
 cl_bool clo_scan_by_key_with_host_data(CloScanByKey* sbk, CCLQueue* cq_exec, CCLQueue* cq_comm,
@@ -175,58 +147,23 @@ cl_bool clo_scan_by_key_with_host_data(CloScanByKey* sbk, CCLQueue* cq_exec, CCL
 	}
 	if (numel == 0) return CL_TRUE;
 
-	cl_bool status = CL_FALSE;
-	CCLBuffer* dev[3] = { NULL, NULL, NULL };   /* keys in, values in, out (the values' buffer itself when in place) */
-	CCLQueue* intern_queue = NULL;
-	CCLEvent* evt = NULL;
-	CCLEventWaitList ewl = NULL;
-	GError* err_internal = NULL;
 	const size_t ks = clo_type_sizeof(sbk->key_type), vs = clo_type_sizeof(sbk->value_type), ss = clo_type_sizeof(sbk->sum_type);
-	const int in_place = values_in != NULL && (const void*) data_out == values_in;
-	const size_t bytes[3] = { numel * ks, numel * vs, numel * ss };
-	const int used[3] = { 1, values_in != NULL, !in_place };
-	CCLContext* ctx = sbk->ctx;
-
-	if (cq_exec == NULL) {
-		CCLDevice* d = ccl_context_get_device(ctx, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		intern_queue = ccl_queue_new(ctx, d, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		cq_exec = intern_queue;
-	}
-	if (cq_comm == NULL) cq_comm = cq_exec;
-	for (int i = 0; i < 3; ++i) {
-		if (!used[i]) continue;
-		dev[i] = ccl_buffer_new(ctx, CL_MEM_READ_WRITE, bytes[i], NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	ccl_buffer_enqueue_write(dev[0], cq_comm, CL_TRUE, 0, bytes[0], (void*) keys_in, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	if (values_in) {
-		ccl_buffer_enqueue_write(dev[1], cq_comm, CL_TRUE, 0, bytes[1], (void*) values_in, NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	evt = clo_scan_by_key_with_device_data(sbk, cq_exec, cq_comm, dev[0], dev[1], in_place ? dev[1] : dev[2], numel, &err_internal);
-	if (err_internal) goto error_handler;
-	ccl_buffer_enqueue_read(in_place ? dev[1] : dev[2], cq_comm, CL_TRUE, 0, bytes[2], data_out, evt ? ccl_ewl(&ewl, evt, NULL) : NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	status = CL_TRUE;
-	goto finish;
-
-error_handler:
-	clo_gerror_propagate(err, err_internal);
-	status = CL_FALSE;
-
-finish:
-	ccl_event_wait_list_clear(&ewl);
-	for (int i = 0; i < 3; ++i) if (dev[i]) ccl_buffer_destroy(dev[i]);
-	if (intern_queue) ccl_queue_destroy(intern_queue);
-	return status;
+	/* keys in, values in, out: in place the values' buffer itself, and no third one */
+	const int out = values_in != NULL && (const void*) data_out == values_in ? 1 : 2;
+	clo_stage st;
+	clo_stage_open(&st, sbk->head.ctx, cq_exec, cq_comm);
+	clo_stage_in(&st, 0, keys_in, numel * ks);
+	clo_stage_in(&st, 1, values_in, numel * vs);
+	if (out == 2) clo_stage_out(&st, 2, data_out, numel * ss);
+	if (clo_stage_ok(&st))
+		st.evt = clo_scan_by_key_with_device_data(sbk, st.cq_exec, st.cq_comm, st.dev[0], st.dev[1], st.dev[out], numel, &st.err);
+	clo_stage_read(&st, out, data_out, numel * ss);
+	return clo_stage_close(&st, err);
 }
 
 CCLContext* clo_scan_by_key_get_context(CloScanByKey* sbk) {
 	clo_return_val_if_fail(sbk != NULL, NULL);
-	return sbk->ctx;
+	return sbk->head.ctx;
 }
 
 CloType clo_scan_by_key_get_key_type(CloScanByKey* sbk) {

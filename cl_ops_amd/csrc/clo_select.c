@@ -1,7 +1,7 @@
 /*
  * clo_select.c — CloSelect (include/clo_select.h; not upstream): stable selection and partition by flags or by
  * comparison with a threshold, with values or as indices. The kernels are reached through the thin C-ABI
- * (clo_hip_select, include/clo_hip.h).
+ * (clo_hip_select, include/clo_hip.h); the host layer is the one the operation drivers share (clo_internal.h).
  *
  * Every argument is checked before anything touches the device, so that the refusals come back the same on a
  * context without one. err may be NULL everywhere.
@@ -9,7 +9,6 @@
 #include "clo_select.h"
 
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "clo_internal.h"
@@ -17,34 +16,19 @@
 #define CLO_SELECT_EVENT "clo_select"
 
 struct clo_select {
-	CCLContext* ctx;
+	clo_op_head head;        /* the workspace: the tiles' kept counts (clo_hip_select_workspace_bytes) */
 	int op;                  /* index in select_ops: what clo_hip_select takes */
 	int pred;                /* index in select_preds, likewise */
 	CloType key_type;
 	size_t value_size;
-	clo_devbuf workspace;    /* the tiles' kept counts (clo_hip_select_workspace_bytes); grows, never shrinks */
-	clo_stream_guard guard;  /* the workspace belongs to one queue at a time */
 };
 
 static const char* const select_ops[] = { "select", "partition" };
 static const char* const select_preds[] = { "flagged", "lt", "le", "gt", "ge", "eq", "ne" };
 
-/* 0 unsigned, 1 signed, 2 IEEE total order: the key kinds of clo_sort_by_key_* */
-static int select_key_kind(CloType t) {
-	if (t == CLO_CHAR || t == CLO_SHORT || t == CLO_INT || t == CLO_LONG) return 1;
-	if (t == CLO_HALF || t == CLO_FLOAT || t == CLO_DOUBLE) return 2;
-	return 0;
-}
-
-static int select_index(const char* name, const char* const* names, int count) {
-	for (int i = 0; name && i < count; ++i)
-		if (!strcmp(name, names[i])) return i;
-	return -1;
-}
-
 CloSelect* clo_select_new(const char* op, const char* pred, const char* options, CCLContext* ctx, CloType key_type, size_t value_size, GError** err) {
 	clo_return_val_if_fail(err == NULL || *err == NULL, NULL);
-	const int opi = select_index(op, select_ops, 2), predi = select_index(pred, select_preds, 7);
+	const int opi = clo_name_index(op, select_ops, 2), predi = clo_name_index(pred, select_preds, 7);
 	if (opi < 0) {
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "Unknown selection op '%s' (one of: " CLO_SELECT_OPS ").", op ? op : "(null)");
 		return NULL;
@@ -69,13 +53,8 @@ CloSelect* clo_select_new(const char* op, const char* pred, const char* options,
 		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "A selection carries values of 0 (none), 4 or 8 bytes, not a value_size of %zu.", value_size);
 		return NULL;
 	}
-	CloSelect* sel = (CloSelect*) calloc(1, sizeof(CloSelect));
-	if (!sel) {
-		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_LIBRARY, "Out of host memory.");
-		return NULL;
-	}
-	ccl_context_ref(ctx);
-	sel->ctx = ctx;
+	CloSelect* sel = (CloSelect*) clo_op_new(sizeof(CloSelect), ctx, err);
+	if (!sel) return NULL;
 	sel->op = opi;
 	sel->pred = predi;
 	sel->key_type = key_type;
@@ -85,18 +64,7 @@ CloSelect* clo_select_new(const char* op, const char* pred, const char* options,
 
 void clo_select_destroy(CloSelect* sel) {
 	clo_return_if_fail(sel != NULL);
-	clo_devbuf_release(&sel->workspace);
-	clo_stream_guard_release(&sel->guard);
-	ccl_context_unref(sel->ctx);
-	free(sel);
-}
-
-typedef struct { const void* p; size_t bytes; } select_range;
-
-static int select_overlap(select_range a, select_range b) {
-	if (!a.p || !b.p || !a.bytes || !b.bytes) return 0;
-	const uintptr_t a0 = (uintptr_t) a.p, b0 = (uintptr_t) b.p;
-	return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+	clo_op_destroy(sel);
 }
 
 /* the bytes flags_or_threshold holds: numel flags, or one key */
@@ -118,14 +86,12 @@ static const char* select_refusal(CloSelect* sel, const void* keys_in, const voi
 	if (numel > 0 && !keys_in && (sel->pred != CLO_HIP_SELECT_FLAGGED || keys_out))
 		return "keys_in is required (only a flagged selection that writes indices alone reads no keys)";
 	const size_t ks = clo_type_sizeof(sel->key_type), vs = sel->value_size;
-	const select_range in[3] = { { keys_in, numel * ks }, { values_in, numel * vs }, { fot, select_fot_bytes(sel, numel) } };
+	const clo_range in[3] = { { keys_in, numel * ks }, { values_in, numel * vs }, { fot, select_fot_bytes(sel, numel) } };
 	/* the outputs are sized by numel rows, whatever k turns out to be */
-	const select_range out[3] = { { keys_out, numel * ks }, { values_out, numel * vs }, { num_out, count_bytes } };
-	for (int o = 0; o < 3; ++o) {
-		for (int i = 0; i < 3; ++i)
-			if (select_overlap(out[o], in[i])) return "an output range overlaps an input range (there is no in-place selection)";
-		for (int p = 0; p < o; ++p)
-			if (select_overlap(out[o], out[p])) return "two output ranges overlap";
+	const clo_range out[3] = { { keys_out, numel * ks }, { values_out, numel * vs }, { num_out, count_bytes } };
+	switch (clo_ranges_conflict(in, 3, out, 3)) {
+		case CLO_RANGES_OUT_IN: return "an output range overlaps an input range (there is no in-place selection)";
+		case CLO_RANGES_OUT_OUT: return "two output ranges overlap";
 	}
 	return NULL;
 }
@@ -138,7 +104,7 @@ CCLEvent* clo_select_with_device_data(CloSelect* sel, CCLQueue* cq_exec, CCLQueu
 	(void) cq_comm;   /* nothing is copied */
 	CCLBuffer* const buf[6] = { keys_in, values_in, flags_or_threshold, keys_out, values_out, num_out };
 	void* p[6];
-	for (int i = 0; i < 6; ++i) p[i] = buf[i] ? ccl_buffer_get_device_ptr(buf[i]) : NULL;
+	clo_buffers_device_ptrs(buf, p, 6);
 	const char* why = select_refusal(sel, p[0], p[1], p[2], p[3], p[4], p[5], numel, sizeof(cl_ulong));
 	if (!why && ((uintptr_t) p[5] & 7u)) why = "num_out must be 8-byte aligned";
 	if (why) {
@@ -147,29 +113,22 @@ CCLEvent* clo_select_with_device_data(CloSelect* sel, CCLQueue* cq_exec, CCLQueu
 	}
 	const size_t ks = clo_type_sizeof(sel->key_type), vs = sel->value_size;
 	const size_t need[6] = { numel * ks, numel * vs, select_fot_bytes(sel, numel), numel * ks, numel * vs, sizeof(cl_ulong) };
-	for (int i = 0; i < 6; ++i) {
-		if (buf[i] && need[i] > ccl_buffer_get_size(buf[i])) {
-			clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "numel (%zu) exceeds the size of the device buffers (the inputs and the outputs "
-				"hold numel rows, the flags numel bytes, the threshold one key, num_out 8 bytes)", numel);
-			return NULL;
-		}
+	if (!clo_buffers_hold(buf, need, 6)) {
+		clo_gerror_set(err, CLO_ERROR, CLO_ERROR_ARGS, "numel (%zu) exceeds the size of the device buffers (the inputs and the outputs "
+			"hold numel rows, the flags numel bytes, the threshold one key, num_out 8 bytes)", numel);
+		return NULL;
 	}
 	clo_return_val_if_fail(cq_exec != NULL, NULL);
 	clo_debug("SELECT: %s %s of %zu keys of type %s, %s", select_ops[sel->op], select_preds[sel->pred], numel, clo_type_get_name(sel->key_type),
 		vs == 0 ? "no values" : !p[1] ? "indices" : vs == 4 ? "4-byte values" : "8-byte values");
 
 	const size_t ws = clo_hip_select_workspace_bytes(numel, (int) ks, (int) vs);
-	if (ws > 0) {
-		if (clo_hip_failed(clo_stream_guard_enter(&sel->guard, cq_exec), err, "hipStreamWaitEvent")) return NULL;
-		if (clo_hip_failed(clo_devbuf_reserve(&sel->workspace, ws), err, "hipMalloc(select workspace)")) return NULL;
-	}
+	if (ws > 0 && !clo_op_reserve(&sel->head, cq_exec, ws, "hipMalloc(select workspace)", err)) return NULL;
 	CCLEvent* evt = ccl_queue_begin_command(cq_exec, CLO_SELECT_EVENT, err);
 	if (!evt) return NULL;
 	const int st = clo_hip_select(sel->op, sel->pred, p[0], p[1], p[2], p[3], p[4], (uint64_t*) p[5], numel,
-		(int) ks, select_key_kind(sel->key_type), (int) vs, sel->workspace.ptr, sel->workspace.bytes, ccl_queue_get_stream(cq_exec));
-	if (clo_hip_failed(st, err, "clo_hip_select")) { ccl_queue_abort_command(cq_exec, evt); return NULL; }
-	if (!ccl_queue_end_command(cq_exec, evt, err)) { ccl_queue_abort_command(cq_exec, evt); return NULL; }
-	return evt;
+		(int) ks, clo_type_key_kind(sel->key_type), (int) vs, sel->head.workspace.ptr, sel->head.workspace.bytes, ccl_queue_get_stream(cq_exec));
+	return clo_op_end_command(cq_exec, evt, st, "clo_hip_select", err);
 }
 
 cl_bool clo_select_with_host_data(CloSelect* sel, CCLQueue* cq_exec, CCLQueue* cq_comm,
@@ -185,70 +144,31 @@ cl_bool clo_select_with_host_data(CloSelect* sel, CCLQueue* cq_exec, CCLQueue* c
 	*num_out = 0;
 	if (numel == 0) return CL_TRUE;   /* nothing can be kept: no device needed */
 
-	cl_bool status = CL_FALSE;
 	const size_t ks = clo_type_sizeof(sel->key_type), vs = sel->value_size;
 	/* keys, values, the flags or the threshold, keys out, values out, the count */
 	const void* const host[6] = { keys_in, values_in, flags_or_threshold, keys_out, values_out, num_out };
 	const size_t bytes[6] = { numel * ks, numel * vs, select_fot_bytes(sel, numel), numel * ks, numel * vs, sizeof(cl_ulong) };
-	CCLBuffer* dev[6] = { NULL, NULL, NULL, NULL, NULL, NULL };
-	CCLQueue* intern_queue = NULL;
-	CCLEvent* evt = NULL;
-	CCLEventWaitList ewl = NULL;
-	GError* err_internal = NULL;
 	cl_ulong k = 0;
-	size_t rows = 0;
-	CCLContext* ctx = sel->ctx;
-
-	if (cq_exec == NULL) {
-		CCLDevice* d = ccl_context_get_device(ctx, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		intern_queue = ccl_queue_new(ctx, d, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		cq_exec = intern_queue;
-	}
-	if (cq_comm == NULL) cq_comm = cq_exec;
-	for (int i = 0; i < 6; ++i) {
-		if (!host[i] || bytes[i] == 0) continue;
-		dev[i] = ccl_buffer_new(ctx, CL_MEM_READ_WRITE, bytes[i], NULL, &err_internal);
-		if (err_internal) goto error_handler;
-		if (i < 3) {
-			ccl_buffer_enqueue_write(dev[i], cq_comm, CL_TRUE, 0, bytes[i], (void*) host[i], NULL, &err_internal);
-			if (err_internal) goto error_handler;
-		}
-	}
-	evt = clo_select_with_device_data(sel, cq_exec, cq_comm, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], numel, &err_internal);
-	if (err_internal) goto error_handler;
+	clo_stage st;
+	clo_stage_open(&st, sel->head.ctx, cq_exec, cq_comm);
+	for (int i = 0; i < 3; ++i) clo_stage_in(&st, i, host[i], bytes[i]);
+	for (int i = 3; i < 6; ++i) clo_stage_out(&st, i, host[i], bytes[i]);
+	if (clo_stage_ok(&st))
+		st.evt = clo_select_with_device_data(sel, st.cq_exec, st.cq_comm, st.dev[0], st.dev[1], st.dev[2], st.dev[3], st.dev[4], st.dev[5], numel, &st.err);
 	/* the count first (blocking): it says how many rows of a select there are to copy */
-	ccl_buffer_enqueue_read(dev[5], cq_comm, CL_TRUE, 0, sizeof(cl_ulong), &k, evt ? ccl_ewl(&ewl, evt, NULL) : NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	if (k > numel) {
-		clo_gerror_set(&err_internal, CLO_ERROR, CLO_ERROR_LIBRARY, "selection: %llu rows kept of %zu", (unsigned long long) k, numel);
-		goto error_handler;
-	}
-	rows = sel->op == CLO_HIP_SELECT_PARTITION ? numel : (size_t) k;
-	for (int i = 3; i < 5; ++i) {
-		if (!dev[i] || rows == 0) continue;
-		ccl_buffer_enqueue_read(dev[i], cq_comm, CL_TRUE, 0, rows * (i == 3 ? ks : vs), (void*) host[i], NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	*num_out = (size_t) k;
-	status = CL_TRUE;
-	goto finish;
-
-error_handler:
-	clo_gerror_propagate(err, err_internal);
-	status = CL_FALSE;
-
-finish:
-	ccl_event_wait_list_clear(&ewl);
-	for (int i = 0; i < 6; ++i) if (dev[i]) ccl_buffer_destroy(dev[i]);
-	if (intern_queue) ccl_queue_destroy(intern_queue);
-	return status;
+	clo_stage_read(&st, 5, &k, sizeof(cl_ulong));
+	if (clo_stage_ok(&st) && k > numel)
+		clo_gerror_set(&st.err, CLO_ERROR, CLO_ERROR_LIBRARY, "selection: %llu rows kept of %zu", (unsigned long long) k, numel);
+	const size_t rows = sel->op == CLO_HIP_SELECT_PARTITION ? numel : (size_t) k;
+	clo_stage_read(&st, 3, keys_out, rows * ks);
+	clo_stage_read(&st, 4, values_out, rows * vs);
+	if (clo_stage_ok(&st)) *num_out = (size_t) k;
+	return clo_stage_close(&st, err);
 }
 
 CCLContext* clo_select_get_context(CloSelect* sel) {
 	clo_return_val_if_fail(sel != NULL, NULL);
-	return sel->ctx;
+	return sel->head.ctx;
 }
 
 CloType clo_select_get_key_type(CloSelect* sel) {

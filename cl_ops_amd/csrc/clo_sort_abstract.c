@@ -282,7 +282,7 @@ CloSort* clo_sort_new(const char* type, const char* options, CCLContext* ctx,
 		CloSortKeySpec* ks = &sorter->spec;
 		ks->elem_size = (int) clo_type_sizeof(sorter->elem_type);
 		ks->key_size = (int) clo_type_sizeof(sorter->key_type);
-		ks->key_kind = clo_type_is_float(sorter->key_type) ? 2 : (clo_type_is_signed(sorter->key_type) ? 1 : 0);
+		ks->key_kind = clo_type_key_kind(sorter->key_type);
 		if (ks->elem_size == 0 || ks->key_size == 0) {
 			clo_gerror_set(err, CLO_ERROR, CLO_ERROR_UNKNOWN_TYPE, "Unknown element or key type");
 			goto error_handler;

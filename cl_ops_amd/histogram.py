@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from ._hip import lib, vp, sz, ci
-from .api import _Err, _b, _sig, _E, _u32, clo_type, CloError, CLO_ERROR_LIBRARY, CLO_TYPES, CLO_TYPE_NP
+from .api import _Err, _b, _h, _p, _sig, _E, _u32, _Handle, _keys_1d, _values_like, clo_type, CloError, CLO_ERROR_LIBRARY, CLO_TYPES, CLO_TYPE_NP
 
 _sig("clo_histogram_new", vp, C.c_char_p, vp, ci, ci, ci, _E)
 _sig("clo_histogram_destroy", None, vp)
@@ -38,19 +38,16 @@ def histogram_lds_bins(sum_size=4):
     return lib.clo_hip_histogram_lds_bins(sum_size)
 
 
-class Histogram:
+class Histogram(_Handle):
     """CloHistogram. value_type None: 'uint' (calls without values ignore it); sum_type None: the value type.
     options: None or 'accumulate'."""
+    _destroy = "clo_histogram_destroy"
 
     def __init__(self, ctx, key_type, value_type=None, sum_type=None, options=None):
         kt = clo_type(key_type)
         vt = clo_type(value_type) if value_type is not None else CLO_TYPES["uint"]
         st = clo_type(sum_type) if sum_type is not None else vt
-        err = _Err()
-        self.h = lib.clo_histogram_new(_b(options), ctx.h, kt, vt, st, err.ref)
-        err.raise_if_set()
-        if not self.h:
-            raise CloError("clo", CLO_ERROR_LIBRARY, "clo_histogram_new returned NULL")
+        self._new("clo_histogram_new", _b(options), ctx.h, kt, vt, st)
         self.ctx = ctx
 
     key_type = property(lambda self: lib.clo_histogram_get_key_type(self.h))
@@ -68,9 +65,8 @@ class Histogram:
     def with_device_data(self, q, keys_in, values_in, hist_out, numel, lower=0, shift=0, num_bins=None, q_comm=None):
         """clo_histogram_with_device_data on Buffers (values_in may be None); asynchronous on q. Returns the event."""
         err = _Err()
-        h = lambda b: b.h if b is not None else None
         lo = self._lower(lower)
-        evt = lib.clo_histogram_with_device_data(self.h, h(q), h(q_comm), h(keys_in), h(values_in), h(hist_out), numel,
+        evt = lib.clo_histogram_with_device_data(self.h, _h(q), _h(q_comm), _h(keys_in), _h(values_in), _h(hist_out), numel,
                                                  lo.ctypes.data_as(vp), shift, num_bins, err.ref)
         err.raise_if_set()
         return evt
@@ -78,30 +74,17 @@ class Histogram:
     def with_host_data(self, keys, values=None, lower=0, shift=0, num_bins=None, out=None, q_exec=None, q_comm=None):
         """clo_histogram_with_host_data: the num_bins sums as a numpy array of the sum type. out: the array the
         results are written to (under 'accumulate': added onto; without one, onto zeros)."""
-        k = np.ascontiguousarray(keys)
-        if k.ndim != 1 or k.itemsize != self.key_size:
-            raise ValueError("keys: a 1-D array of %d-byte elements" % self.key_size)
-        v = None
-        if values is not None:
-            v = np.ascontiguousarray(values)
-            if v.shape != k.shape or v.itemsize != self.value_size:
-                raise ValueError("values: %d-byte elements, as many as keys" % self.value_size)
+        k = _keys_1d(keys, self.key_size, "keys")
+        v = _values_like(values, k, self.value_size, "values")
         st = CLO_TYPE_NP[_TYPE_NAMES[self.sum_type]]
         if out is None:
             out = np.zeros(num_bins, dtype=st)
         elif out.dtype != np.dtype(st) or out.ndim != 1 or out.size != num_bins or not out.flags.c_contiguous:
             raise ValueError("out: a contiguous 1-D array of num_bins elements of the sum type")
         lo = self._lower(lower)
-        p = lambda a: a.ctypes.data_as(vp) if a is not None else None
         err = _Err()
-        ok = lib.clo_histogram_with_host_data(self.h, q_exec.h if q_exec else None, q_comm.h if q_comm else None,
-                                              p(k), p(v), p(out), k.size, p(lo), shift, num_bins, err.ref)
+        ok = lib.clo_histogram_with_host_data(self.h, _h(q_exec), _h(q_comm), _p(k), _p(v), _p(out), k.size, _p(lo), shift, num_bins, err.ref)
         err.raise_if_set()
         if not ok:
             raise CloError("clo", CLO_ERROR_LIBRARY, "clo_histogram_with_host_data failed")
         return out
-
-    def close(self):
-        if self.h:
-            lib.clo_histogram_destroy(self.h)
-            self.h = None

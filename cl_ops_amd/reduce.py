@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from ._hip import lib, vp, sz, ci
-from .api import _Err, _b, _sig, _E, _u32, clo_type, CloError, CLO_ERROR_LIBRARY, CLO_TYPES, CLO_TYPE_NP
+from .api import _Err, _b, _h, _p, _sig, _E, _u32, _Handle, _keys_1d, _values_like, clo_type, CloError, CLO_ERROR_LIBRARY, CLO_TYPES, CLO_TYPE_NP
 
 _sig("clo_reduce_by_key_new", vp, C.c_char_p, C.c_char_p, vp, ci, ci, ci, _E)
 _sig("clo_reduce_by_key_destroy", None, vp)
@@ -32,18 +32,15 @@ def reduce_by_key_tile(key_size, value_size=0):
     return lib.clo_hip_reduce_by_key_tile(key_size, value_size)
 
 
-class ReduceByKey:
+class ReduceByKey(_Handle):
     """CloReduceByKey. value_type None: 'uint' (calls without values ignore it); sum_type None: the value type."""
+    _destroy = "clo_reduce_by_key_destroy"
 
     def __init__(self, ctx, key_type, value_type=None, sum_type=None, op="sum", options=None):
         kt = clo_type(key_type)
         vt = clo_type(value_type) if value_type is not None else CLO_TYPES["uint"]
         st = clo_type(sum_type) if sum_type is not None else vt
-        err = _Err()
-        self.h = lib.clo_reduce_by_key_new(_b(op), _b(options), ctx.h, kt, vt, st, err.ref)
-        err.raise_if_set()
-        if not self.h:
-            raise CloError("clo", CLO_ERROR_LIBRARY, "clo_reduce_by_key_new returned NULL")
+        self._new("clo_reduce_by_key_new", _b(op), _b(options), ctx.h, kt, vt, st)
         self.ctx = ctx
 
     key_type = property(lambda self: lib.clo_reduce_by_key_get_key_type(self.h))
@@ -58,36 +55,22 @@ class ReduceByKey:
         """clo_reduce_by_key_with_device_data on Buffers (values_in, keys_out or aggr_out may be None); asynchronous on
         q. num_runs_out: a Buffer of one uint64. Returns the event."""
         err = _Err()
-        h = lambda b: b.h if b is not None else None
-        evt = lib.clo_reduce_by_key_with_device_data(self.h, h(q), h(q_comm), h(keys_in), h(values_in), h(keys_out),
-                                                     h(aggr_out), h(num_runs_out), numel, err.ref)
+        evt = lib.clo_reduce_by_key_with_device_data(self.h, _h(q), _h(q_comm), _h(keys_in), _h(values_in), _h(keys_out),
+                                                     _h(aggr_out), _h(num_runs_out), numel, err.ref)
         err.raise_if_set()
         return evt
 
     def with_host_data(self, keys, values=None, q_exec=None, q_comm=None, want_keys=True, want_aggr=True):
         """clo_reduce_by_key_with_host_data: (keys_out[:m], aggr_out[:m]) as numpy arrays, None for an output that
         was not asked for."""
-        k = np.ascontiguousarray(keys)
-        if k.ndim != 1 or k.itemsize != self.key_size:
-            raise ValueError("keys: a 1-D array of %d-byte elements" % self.key_size)
-        v = None
-        if values is not None:
-            v = np.ascontiguousarray(values)
-            if v.shape != k.shape or v.itemsize != self.value_size:
-                raise ValueError("values: %d-byte elements, as many as keys" % self.value_size)
+        k = _keys_1d(keys, self.key_size, "keys")
+        v = _values_like(values, k, self.value_size, "values")
         ko = np.empty_like(k) if want_keys else None
         ao = np.empty(k.shape, dtype=CLO_TYPE_NP[_TYPE_NAMES[self.sum_type]]) if want_aggr else None
         m = sz(0)
-        p = lambda a: a.ctypes.data_as(vp) if a is not None else None
         err = _Err()
-        ok = lib.clo_reduce_by_key_with_host_data(self.h, q_exec.h if q_exec else None, q_comm.h if q_comm else None,
-                                                  p(k), p(v), p(ko), p(ao), C.byref(m), k.size, err.ref)
+        ok = lib.clo_reduce_by_key_with_host_data(self.h, _h(q_exec), _h(q_comm), _p(k), _p(v), _p(ko), _p(ao), C.byref(m), k.size, err.ref)
         err.raise_if_set()
         if not ok:
             raise CloError("clo", CLO_ERROR_LIBRARY, "clo_reduce_by_key_with_host_data failed")
         return (ko[:m.value] if ko is not None else None), (ao[:m.value] if ao is not None else None)
-
-    def close(self):
-        if self.h:
-            lib.clo_reduce_by_key_destroy(self.h)
-            self.h = None

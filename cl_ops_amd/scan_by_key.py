@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from ._hip import lib, vp, sz, ci
-from .api import _Err, _b, _sig, _E, _u32, clo_type, CloError, CLO_ERROR_LIBRARY, CLO_TYPES, CLO_TYPE_NP
+from .api import _Err, _b, _h, _p, _sig, _E, _u32, _Handle, _keys_1d, clo_type, CloError, CLO_ERROR_LIBRARY, CLO_TYPES, CLO_TYPE_NP
 
 _sig("clo_scan_by_key_new", vp, C.c_char_p, C.c_char_p, vp, ci, ci, ci, _E)
 _sig("clo_scan_by_key_destroy", None, vp)
@@ -33,20 +33,17 @@ def scan_by_key_tile(key_size, value_size=0):
     return lib.clo_hip_scan_by_key_tile(key_size, value_size)
 
 
-class ScanByKey:
+class ScanByKey(_Handle):
     """CloScanByKey. value_type None: 'uint' (calls without values ignore it); sum_type None: the value type.
     inclusive: the option string "inclusive=1" of the C API."""
+    _destroy = "clo_scan_by_key_destroy"
 
     def __init__(self, ctx, key_type, value_type=None, sum_type=None, op="sum", inclusive=False):
         kt = clo_type(key_type)
         vt = clo_type(value_type) if value_type is not None else CLO_TYPES["uint"]
         st = clo_type(sum_type) if sum_type is not None else vt
         options = "inclusive=1" if inclusive else None
-        err = _Err()
-        self.h = lib.clo_scan_by_key_new(_b(op), _b(options), ctx.h, kt, vt, st, err.ref)
-        err.raise_if_set()
-        if not self.h:
-            raise CloError("clo", CLO_ERROR_LIBRARY, "clo_scan_by_key_new returned NULL")
+        self._new("clo_scan_by_key_new", _b(op), _b(options), ctx.h, kt, vt, st)
         self.ctx = ctx
 
     key_type = property(lambda self: lib.clo_scan_by_key_get_key_type(self.h))
@@ -62,17 +59,14 @@ class ScanByKey:
         """clo_scan_by_key_with_device_data on Buffers (values_in may be None; data_out may be values_in itself when
         the sum type is as wide as the value type); asynchronous on q. Returns the event."""
         err = _Err()
-        h = lambda b: b.h if b is not None else None
-        evt = lib.clo_scan_by_key_with_device_data(self.h, h(q), h(q_comm), h(keys_in), h(values_in), h(data_out), numel, err.ref)
+        evt = lib.clo_scan_by_key_with_device_data(self.h, _h(q), _h(q_comm), _h(keys_in), _h(values_in), _h(data_out), numel, err.ref)
         err.raise_if_set()
         return evt
 
     def with_host_data(self, keys, values=None, q_exec=None, q_comm=None, out=None):
         """clo_scan_by_key_with_host_data: the results as a numpy array of the sum type. out: an array to write them
         to (`values` itself for the in-place form) instead of a new one."""
-        k = np.ascontiguousarray(keys)
-        if k.ndim != 1 or k.itemsize != self.key_size:
-            raise ValueError("keys: a 1-D array of %d-byte elements" % self.key_size)
+        k = _keys_1d(keys, self.key_size, "keys")
         v = None
         if values is not None:
             v = values if out is values else np.ascontiguousarray(values)
@@ -82,16 +76,9 @@ class ScanByKey:
             out = np.empty(k.shape, dtype=CLO_TYPE_NP[_TYPE_NAMES[self.sum_type]])
         elif out.shape != k.shape or out.itemsize != self.sum_size or not out.flags.c_contiguous:
             raise ValueError("out: a contiguous array of %d-byte elements, as many as keys" % self.sum_size)
-        p = lambda a: a.ctypes.data_as(vp) if a is not None else None
         err = _Err()
-        ok = lib.clo_scan_by_key_with_host_data(self.h, q_exec.h if q_exec else None, q_comm.h if q_comm else None,
-                                                p(k), p(v), p(out), k.size, err.ref)
+        ok = lib.clo_scan_by_key_with_host_data(self.h, _h(q_exec), _h(q_comm), _p(k), _p(v), _p(out), k.size, err.ref)
         err.raise_if_set()
         if not ok:
             raise CloError("clo", CLO_ERROR_LIBRARY, "clo_scan_by_key_with_host_data failed")
         return out
-
-    def close(self):
-        if self.h:
-            lib.clo_scan_by_key_destroy(self.h)
-            self.h = None

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._hip import lib, vp, sz, ci
-from .api import _Err, _b, _sig, _E, _u32, clo_type, CloError, CLO_ERROR_LIBRARY
+from .api import _Err, _b, _h, _p, _sig, _E, _u32, _Handle, _keys_1d, clo_type, CloError, CLO_ERROR_LIBRARY
 
 SEARCH_UPPER = 1
 SEARCH_NEEDLES_SORTED = 2
@@ -43,15 +43,12 @@ def _flags(upper, needles_sorted):
     return (SEARCH_UPPER if upper else 0) | (SEARCH_NEEDLES_SORTED if needles_sorted else 0)
 
 
-class Search:
+class Search(_Handle):
     """CloSearch. upper: upper instead of lower bounds; needles_sorted: the caller's promise that the needles ascend."""
+    _destroy = "clo_search_destroy"
 
     def __init__(self, ctx, key_type, options=None):
-        err = _Err()
-        self.h = lib.clo_search_new(_b(options), ctx.h, clo_type(key_type), err.ref)
-        err.raise_if_set()
-        if not self.h:
-            raise CloError("clo", CLO_ERROR_LIBRARY, "clo_search_new returned NULL")
+        self._new("clo_search_new", _b(options), ctx.h, clo_type(key_type))
         self.ctx = ctx
 
     key_type = property(lambda self: lib.clo_search_get_key_type(self.h))
@@ -61,34 +58,21 @@ class Search:
         """clo_search_with_device_data on Buffers (haystack may be None with numel_h 0); asynchronous on q. Returns
         the event."""
         err = _Err()
-        h = lambda b: b.h if b is not None else None
-        evt = lib.clo_search_with_device_data(self.h, h(q), h(q_comm), h(haystack), numel_h, h(needles), numel_n,
-                                              _flags(upper, needles_sorted), h(pos_out), err.ref)
+        evt = lib.clo_search_with_device_data(self.h, _h(q), _h(q_comm), _h(haystack), numel_h, _h(needles), numel_n,
+                                              _flags(upper, needles_sorted), _h(pos_out), err.ref)
         err.raise_if_set()
         return evt
 
-    def _keys(self, keys, what):
-        k = np.ascontiguousarray(keys)
-        if k.ndim != 1 or k.itemsize != self.key_size:
-            raise ValueError("%s: a 1-D array of %d-byte elements" % (what, self.key_size))
-        return k
-
     def with_host_data(self, haystack, needles, upper=False, needles_sorted=False, q_exec=None, q_comm=None):
         """clo_search_with_host_data: the positions as a numpy array of uint32, one per needle."""
-        hs, nd = self._keys(haystack, "haystack"), self._keys(needles, "needles")
+        hs, nd = _keys_1d(haystack, self.key_size, "haystack"), _keys_1d(needles, self.key_size, "needles")
         if hs.dtype != nd.dtype:
             raise ValueError("haystack and needles: one dtype")
         pos = np.empty(nd.size, dtype=np.uint32)
         err = _Err()
-        ok = lib.clo_search_with_host_data(self.h, q_exec.h if q_exec else None, q_comm.h if q_comm else None,
-                                           hs.ctypes.data_as(vp), hs.size, nd.ctypes.data_as(vp), nd.size,
-                                           _flags(upper, needles_sorted), pos.ctypes.data_as(vp), err.ref)
+        ok = lib.clo_search_with_host_data(self.h, _h(q_exec), _h(q_comm), _p(hs), hs.size, _p(nd), nd.size,
+                                           _flags(upper, needles_sorted), _p(pos), err.ref)
         err.raise_if_set()
         if not ok:
             raise CloError("clo", CLO_ERROR_LIBRARY, "clo_search_with_host_data failed")
         return pos
-
-    def close(self):
-        if self.h:
-            lib.clo_search_destroy(self.h)
-            self.h = None

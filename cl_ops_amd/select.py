@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from ._hip import lib, vp, sz, ci
-from .api import _Err, _b, _sig, _E, _u32, clo_type, CloError, CLO_ERROR_LIBRARY
+from .api import _Err, _b, _h, _p, _sig, _E, _u32, _Handle, _keys_1d, _values_like, clo_type, CloError, CLO_ERROR_LIBRARY
 
 _sig("clo_select_new", vp, C.c_char_p, C.c_char_p, C.c_char_p, vp, ci, sz, _E)
 _sig("clo_select_destroy", None, vp)
@@ -33,16 +33,13 @@ def select_tile(key_size, value_size=0):
     return lib.clo_hip_select_tile(key_size, value_size)
 
 
-class Select:
+class Select(_Handle):
     """CloSelect. op: one of SELECT_OPS, pred: one of SELECT_PREDS. value_size: 0 (keys only), 4 or 8 bytes per value;
     with 4 and no values the calls write the elements' indices."""
+    _destroy = "clo_select_destroy"
 
     def __init__(self, op, pred, ctx, key_type, value_size=0, options=None):
-        err = _Err()
-        self.h = lib.clo_select_new(_b(op), _b(pred), _b(options), ctx.h, clo_type(key_type), value_size, err.ref)
-        err.raise_if_set()
-        if not self.h:
-            raise CloError("clo", CLO_ERROR_LIBRARY, "clo_select_new returned NULL")
+        self._new("clo_select_new", _b(op), _b(pred), _b(options), ctx.h, clo_type(key_type), value_size)
         self.ctx = ctx
 
     key_type = property(lambda self: lib.clo_select_get_key_type(self.h))
@@ -55,9 +52,8 @@ class Select:
         """clo_select_with_device_data on Buffers (any of which may be None where the contract allows NULL);
         asynchronous on q. Returns the event."""
         err = _Err()
-        h = lambda b: b.h if b is not None else None
-        evt = lib.clo_select_with_device_data(self.h, h(q), h(q_comm), h(keys_in), h(values_in), h(flags_or_threshold),
-                                              h(keys_out), h(values_out), h(num_out), numel, err.ref)
+        evt = lib.clo_select_with_device_data(self.h, _h(q), _h(q_comm), _h(keys_in), _h(values_in), _h(flags_or_threshold),
+                                              _h(keys_out), _h(values_out), _h(num_out), numel, err.ref)
         err.raise_if_set()
         return evt
 
@@ -73,9 +69,7 @@ class Select:
                 raise ValueError("flags: a 1-D array of bytes")
         k = None
         if keys is not None:
-            k = np.ascontiguousarray(keys)
-            if k.ndim != 1 or k.itemsize != self.key_size:
-                raise ValueError("keys: a 1-D array of %d-byte elements" % self.key_size)
+            k = _keys_1d(keys, self.key_size, "keys")
             if not flagged:
                 f = np.ascontiguousarray(flags_or_threshold, dtype=k.dtype).reshape(-1)
                 if f.size != 1:
@@ -85,27 +79,16 @@ class Select:
         n = k.size if k is not None else f.size
         if flagged and f.size != n:
             raise ValueError("flags: as many as keys")
-        v = None
-        if values is not None:
-            v = np.ascontiguousarray(values)
-            if v.shape != (n,) or v.itemsize != self.value_size or self.value_size == 0:
-                raise ValueError("values: %d-byte elements, as many as keys" % self.value_size)
+        v = _values_like(values, k if k is not None else f, self.value_size, "values")
         ko = np.empty(n, dtype=k.dtype) if keys_out and k is not None else None
         vo = None
         if self.value_size:
             vo = np.empty(n, dtype=v.dtype if v is not None else (np.uint32 if self.value_size == 4 else np.uint64))
-        p = lambda a: a.ctypes.data_as(vp) if a is not None else None
         num = sz(0)
         err = _Err()
-        ok = lib.clo_select_with_host_data(self.h, q_exec.h if q_exec else None, q_comm.h if q_comm else None,
-                                           p(k), p(v), p(f), p(ko), p(vo), n, C.byref(num), err.ref)
+        ok = lib.clo_select_with_host_data(self.h, _h(q_exec), _h(q_comm), _p(k), _p(v), _p(f), _p(ko), _p(vo), n, C.byref(num), err.ref)
         err.raise_if_set()
         if not ok:
             raise CloError("clo", CLO_ERROR_LIBRARY, "clo_select_with_host_data failed")
         rows = n if self.op == "partition" else num.value
         return (ko[:rows] if ko is not None else None), (vo[:rows] if vo is not None else None), num.value
-
-    def close(self):
-        if self.h:
-            lib.clo_select_destroy(self.h)
-            self.h = None

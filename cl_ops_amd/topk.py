@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from ._hip import lib, vp, sz, ci
-from .api import _Err, _b, _sig, _E, _u32, clo_type, CloError, CLO_ERROR_LIBRARY
+from .api import _Err, _b, _h, _p, _sig, _E, _u32, _Handle, _keys_1d, _values_like, clo_type, CloError, CLO_ERROR_LIBRARY
 
 _sig("clo_topk_new", vp, C.c_char_p, C.c_char_p, C.c_char_p, vp, ci, sz, _E)
 _sig("clo_topk_destroy", None, vp)
@@ -46,16 +46,13 @@ def topk_sorted_max(key_size, value_size=0):
     return lib.clo_hip_topk_sorted_max(key_size, value_size)
 
 
-class TopK:
+class TopK(_Handle):
     """CloTopK. which: one of TOPK_WHICH, order: one of TOPK_ORDERS. value_size: 0 (keys only), 4 or 8 bytes per value;
     with 4 and no values the calls write the elements' indices."""
+    _destroy = "clo_topk_destroy"
 
     def __init__(self, which, order, ctx, key_type, value_size=0, options=None):
-        err = _Err()
-        self.h = lib.clo_topk_new(_b(which), _b(order), _b(options), ctx.h, clo_type(key_type), value_size, err.ref)
-        err.raise_if_set()
-        if not self.h:
-            raise CloError("clo", CLO_ERROR_LIBRARY, "clo_topk_new returned NULL")
+        self._new("clo_topk_new", _b(which), _b(order), _b(options), ctx.h, clo_type(key_type), value_size)
         self.ctx = ctx
 
     key_type = property(lambda self: lib.clo_topk_get_key_type(self.h))
@@ -68,9 +65,8 @@ class TopK:
         """clo_topk_with_device_data on Buffers (any of which may be None where the contract allows NULL); asynchronous
         on q. Returns the event (None where min(k, numel) is 0 only if the call failed: errors raise)."""
         err = _Err()
-        h = lambda b: b.h if b is not None else None
-        evt = lib.clo_topk_with_device_data(self.h, h(q), h(q_comm), h(keys_in), h(values_in), h(keys_out), h(values_out),
-                                            h(kth_out), numel, k, err.ref)
+        evt = lib.clo_topk_with_device_data(self.h, _h(q), _h(q_comm), _h(keys_in), _h(values_in), _h(keys_out), _h(values_out),
+                                            _h(kth_out), numel, k, err.ref)
         err.raise_if_set()
         return evt
 
@@ -78,31 +74,18 @@ class TopK:
         """clo_topk_with_host_data: (keys, values, kth) as numpy arrays of m = min(k, len(keys)) rows. keys: None with
         keys_out=False. values: the rows' values, their indices when an object made with value_size 4 is given no
         values, None with value_size 0. kth: the k-th key as a 0-d array, None with kth=False or m == 0."""
-        a = np.ascontiguousarray(keys)
-        if a.ndim != 1 or a.itemsize != self.key_size:
-            raise ValueError("keys: a 1-D array of %d-byte elements" % self.key_size)
+        a = _keys_1d(keys, self.key_size, "keys")
         n = a.size
         m = min(int(k), n)
-        v = None
-        if values is not None:
-            v = np.ascontiguousarray(values)
-            if v.shape != (n,) or v.itemsize != self.value_size or self.value_size == 0:
-                raise ValueError("values: %d-byte elements, as many as keys" % self.value_size)
+        v = _values_like(values, a, self.value_size, "values")
         ko = np.empty(m, dtype=a.dtype) if keys_out else None
         vo = None
         if self.value_size:
             vo = np.empty(m, dtype=v.dtype if v is not None else (np.uint32 if self.value_size == 4 else np.uint64))
         kt = np.zeros(1, dtype=a.dtype) if kth else None
-        p = lambda x: x.ctypes.data_as(vp) if x is not None else None
         err = _Err()
-        ok = lib.clo_topk_with_host_data(self.h, q_exec.h if q_exec else None, q_comm.h if q_comm else None,
-                                         p(a), p(v), p(ko), p(vo), p(kt), n, int(k), err.ref)
+        ok = lib.clo_topk_with_host_data(self.h, _h(q_exec), _h(q_comm), _p(a), _p(v), _p(ko), _p(vo), _p(kt), n, int(k), err.ref)
         err.raise_if_set()
         if not ok:
             raise CloError("clo", CLO_ERROR_LIBRARY, "clo_topk_with_host_data failed")
         return ko, vo, (kt[0] if kt is not None and m > 0 else None)
-
-    def close(self):
-        if self.h:
-            lib.clo_topk_destroy(self.h)
-            self.h = None

@@ -459,6 +459,27 @@ def test_host_data_form(dev):
     h.close()
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 elements; the transfers on a queue of their own, then no queue at all (the call makes and destroys
+    one); plain and accumulating, which uploads the output first."""
+    clo, ctx, q = dev
+    n = 2 * tile_of(dev, "short", "int") + 1
+    keys = make_keys("short", "uniform", n, -300, 1, 400, seed=5)
+    values = make_values("int", n, 6)
+    want = histogram(keys, values, np.int64, -300, 1, 333)
+    qc = clo.Queue(ctx)
+    try:
+        for options in (None, "accumulate"):
+            h = clo.Histogram(ctx, "short", "int", "long", options=options)
+            for qe, qcomm in ((q, qc), (None, None)):
+                out = np.arange(333, dtype=np.int64)
+                h.with_host_data(keys, values, lower=-300, shift=1, num_bins=333, out=out, q_exec=qe, q_comm=qcomm)
+                assert np.array_equal(out, want + np.arange(333) if options else want), (options, qe is None, qcomm is None)
+            h.close()
+    finally:
+        qc.close()
+
+
 def test_thin_abi_status_codes(dev):
     clo, ctx, q = dev
     from cl_ops_amd._hip import lib, CLO_HIP_EARGS, CLO_HIP_EUNSUPPORTED

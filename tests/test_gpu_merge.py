@@ -309,6 +309,27 @@ def test_host_data_form(dev, mode):
         assert np.array_equal(vo, np.concatenate((va, vb))[p] if va is not None else p)
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 merged elements; the transfers on a queue of their own, then no queue at all (the call makes and
+    destroys one); with values and as argmerge."""
+    clo, ctx, q = dev
+    qc = clo.Queue(ctx)
+    try:
+        for mode in ("v4", "arg"):
+            T = tile_of(dev, "int", mode)
+            a, b = keys_of_type("int", T + 1, 3), keys_of_type("int", T, 4)
+            va, vb = values_for(mode, a.size, b.size)
+            want_k, p = merge(a, b)
+            m = clo.Merge(ctx, "int", _VS[mode])
+            for qe, qcomm in ((q, qc), (None, None)):
+                ko, vo = m.with_host_data(a, b, va, vb, q_exec=qe, q_comm=qcomm)
+                assert np.array_equal(ko, want_k), (mode, qe is None, qcomm is None)
+                assert np.array_equal(vo, np.concatenate((va, vb))[p] if va is not None else p), (mode, qe is None, qcomm is None)
+            m.close()
+    finally:
+        qc.close()
+
+
 def test_thin_abi_status_codes(dev):
     clo, ctx, q = dev
     from cl_ops_amd._hip import lib

@@ -312,6 +312,28 @@ def test_host_data_form(dev):
     r.close()
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 elements; the transfers on a queue of their own, then no queue at all (the call makes and destroys
+    one). The run count is read first and says how many rows are copied: many runs, one run, and no run at all (the
+    only input without a run is the empty one)."""
+    clo, ctx, q = dev
+    tile = tile_of(dev, "uint", "int")
+    n = 2 * tile + 1
+    keys = make_keys("uint", structure("geo100", n, tile, seed=25), seed=8)
+    values = make_values("int", n, 26)
+    r = clo.ReduceByKey(ctx, "uint", "int", "long", op="sum")
+    qc = clo.Queue(ctx)
+    try:
+        for qe, qcomm in ((q, qc), (None, None)):
+            for k in (keys, np.full(n, 7, np.uint32), keys[:0]):
+                ko, ao = r.with_host_data(k, values[:k.size], q_exec=qe, q_comm=qcomm)
+                wk, wa, m = rbk(k, values[:k.size], "sum", np.int64)
+                assert ko.size == m == ao.size and np.array_equal(ko, wk) and np.array_equal(ao, wa), (qe is None, qcomm is None, k.size)
+    finally:
+        r.close()
+        qc.close()
+
+
 def test_sort_by_key_then_reduce_by_key_on_one_queue(dev):
     """The pipeline this exists for: no host synchronisation between the two calls."""
     clo, ctx, q = dev

@@ -263,6 +263,27 @@ def test_host_data_form(dev):
     r.close()
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 elements; the transfers on a queue of their own, then no queue at all (the call makes and destroys
+    one); into a new array and in place, where the values' device buffer is the output too."""
+    clo, ctx, q = dev
+    tile = tile_of(dev, "uint", "int")
+    n = 2 * tile + 1
+    keys = make_keys("uint", structure("geo100", n, tile, seed=25), seed=8)
+    values = make_values("int", n, 26)
+    want = sbk(keys, values, "sum", np.int32)
+    r = clo.ScanByKey(ctx, "uint", "int", "int")
+    qc = clo.Queue(ctx)
+    try:
+        for qe, qcomm in ((q, qc), (None, None)):
+            assert np.array_equal(r.with_host_data(keys, values, q_exec=qe, q_comm=qcomm), want), (qe is None, qcomm is None)
+            mine = values.copy()
+            assert r.with_host_data(keys, mine, q_exec=qe, q_comm=qcomm, out=mine) is mine and np.array_equal(mine, want), (qe is None, qcomm is None)
+    finally:
+        r.close()
+        qc.close()
+
+
 def _view(region, dtype, count):
     raw = region.base.read(region.q, np.uint8, region.host.size)
     return raw[region.at:region.at + count * np.dtype(dtype).itemsize].copy().view(dtype)

@@ -367,6 +367,26 @@ def test_host_data_form(dev):
         s.close()
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 needles; the transfers on a queue of their own, then no queue at all (the call makes and destroys
+    one); with a haystack and with an empty one, which is not uploaded at all."""
+    clo, ctx, q = dev
+    T, L, P = sizes_of(dev, "int")
+    hay, ndl = keys_of_type("int", 2 * L + 1, 3), keys_of_type("int", 2 * T + 1, 4)
+    mixed = ndl[np.random.default_rng(6).permutation(ndl.size)]
+    s = clo.Search(ctx, "int")
+    qc = clo.Queue(ctx)
+    try:
+        for qe, qcomm in ((q, qc), (None, None)):
+            for upper in (False, True):
+                assert np.array_equal(s.with_host_data(hay, mixed, upper=upper, q_exec=qe, q_comm=qcomm), search(hay, mixed, upper)), (qe is None, qcomm is None, upper)
+            assert np.array_equal(s.with_host_data(hay, ndl, needles_sorted=True, q_exec=qe, q_comm=qcomm), search(hay, ndl, False)), (qe is None, qcomm is None)
+            assert not s.with_host_data(hay[:0], mixed, upper=True, q_exec=qe, q_comm=qcomm).any(), (qe is None, qcomm is None)
+    finally:
+        s.close()
+        qc.close()
+
+
 def test_thin_abi_status_codes(dev):
     clo, ctx, q = dev
     from cl_ops_amd._hip import lib

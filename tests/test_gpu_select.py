@@ -321,6 +321,33 @@ def test_host_data_form(dev, mode):
     s.close()
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 elements; the transfers on a queue of their own, then no queue at all (the call makes and destroys
+    one). The count is read first and says how many rows of a select are copied (all numel of a partition): flags and a
+    threshold that keep some, and ones that keep none."""
+    clo, ctx, q = dev
+    T = tile_of(dev, "int", "v4")
+    keys = np.random.default_rng(2).permutation(keys_of_type("int", 2 * T + 1, 3))
+    vals = values_for("v4", keys.size)
+    flags = (np.arange(keys.size) % 5 == 1).astype(np.uint8)
+    qc = clo.Queue(ctx)
+    try:
+        for op in OPS:
+            for pred, some, none in (("flagged", flags, np.zeros_like(flags)), ("gt", keys[7], keys.max())):   # nothing is above the largest
+                s = clo.Select(op, pred, ctx, "int", 4)
+                for qe, qcomm in ((q, qc), (None, None)):
+                    for fot in (some, none):
+                        ko, vo, k = s.with_host_data(keys, fot, vals, q_exec=qe, q_comm=qcomm)
+                        p, want_k = select(op, pred, keys, fot)
+                        what = (op, pred, qe is None, qcomm is None, fot is none)
+                        assert k == want_k and np.array_equal(ko, keys[p]) and np.array_equal(vo, vals[p]), what
+                        if fot is none:
+                            assert k == 0 and ko.size == (keys.size if op == "partition" else 0), what
+                s.close()
+    finally:
+        qc.close()
+
+
 def test_thin_abi_status_codes(dev):
     clo, ctx, q = dev
     from cl_ops_amd._hip import lib

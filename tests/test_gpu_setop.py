@@ -297,6 +297,32 @@ def test_host_data_form(dev, mode):
         s.close()
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 elements in all; the transfers on a queue of their own, then no queue at all (the call makes and
+    destroys one). The count is read first and says how many rows are copied: inputs that share keys, and inputs whose
+    result is empty (the intersection of disjoint arrays, the difference and the symmetric difference of equal ones)."""
+    clo, ctx, q = dev
+    T = tile_of(dev, "int", "v4")
+    a, b = keys_of_type("int", T + 1, 3), keys_of_type("int", T, 4)
+    low, high = np.arange(T + 1, dtype=np.int32), np.arange(T, dtype=np.int32) + np.int32(5 * T)
+    qc = clo.Queue(ctx)
+    try:
+        for op in OPS:
+            s = clo.SetOp(op, ctx, "int", 4)
+            for qe, qcomm in ((q, qc), (None, None)):
+                for x, y in ((a, b), (low, high) if op == "intersection" else (low, low)):
+                    vx, vy = values_for("v4", x.size, y.size)
+                    ko, vo = s.with_host_data(x, y, vx, vy if keeps_b(op) else None, q_exec=qe, q_comm=qcomm)
+                    want_k, p = setop(op, x, y)
+                    what = (op, qe is None, qcomm is None, x is a)
+                    assert np.array_equal(ko, want_k) and np.array_equal(vo, np.concatenate((vx, vy))[p]), what
+                    if x is not a and op in ("intersection", "difference", "symmetric_difference"):
+                        assert ko.size == 0 and vo.size == 0, what
+            s.close()
+    finally:
+        qc.close()
+
+
 def test_thin_abi_status_codes(dev):
     clo, ctx, q = dev
     from cl_ops_amd._hip import lib

@@ -439,6 +439,28 @@ def test_host_data_form(dev, mode):
             s.close()
 
 
+def test_host_data_form_with_a_queue_for_the_transfers(dev):
+    """2 tiles + 1 elements; the transfers on a queue of their own, then no queue at all (the call makes and destroys
+    one); both orders, with values."""
+    clo, ctx, q = dev
+    T = tile_of(dev, "int", "v4")
+    keys = np.random.default_rng(2).permutation(keys_of_type("int", 2 * T + 1, 3))
+    vals = values_for("v4", keys.size)
+    qc = clo.Queue(ctx)
+    try:
+        for which in WHICH:
+            for order, k in (("input", T + 5), ("sorted", 500)):
+                s = clo.TopK(which, order, ctx, "int", 4)
+                p, want_kth = topk(which, order, keys, k)
+                for qe, qcomm in ((q, qc), (None, None)):
+                    ko, vo, kth = s.with_host_data(keys, k, vals, q_exec=qe, q_comm=qcomm)
+                    what = (which, order, qe is None, qcomm is None)
+                    assert np.array_equal(ko, keys[p]) and np.array_equal(vo, vals[p]) and kth == want_kth[0], what
+                s.close()
+    finally:
+        qc.close()
+
+
 def test_thin_abi_status_codes(dev):
     clo, ctx, q = dev
     from cl_ops_amd._hip import lib
