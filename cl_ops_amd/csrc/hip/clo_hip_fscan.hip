@@ -15,6 +15,8 @@
 //   right, a wave scans its 64 thread sums (shuffle tree), the 4 wave sums are
 //   added left to right; tiles are combined by the same procedure one level up
 //   (4096 tile sums per upper tile; three levels cover any array).
+// tests/fscan_model.py restates this order in numpy, down to the operands of every addition; the GPU tests hold
+// every result to it bit for bit, so a change of the order here is a change of the contract (include/clo_hip.h).
 // Upstream's order is the Blelloch tree of its own work-group shape, so results
 // agree with it to rounding, not bit for bit (no two work-group sizes of upstream
 // agree bit for bit either); like upstream's down-sweep, no step subtracts. 3 element

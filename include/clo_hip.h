@@ -149,7 +149,20 @@ int clo_hip_scan_exclusive_carry(const void* data_in, void* data_out, size_t num
  * sum type on load as upstream's kernels do (scan/clo_scan_blelloch.cl:79-80).
  * Reduce / scan the tile sums / apply, every addition in an order fixed by the
  * layout alone: deterministic, equal to upstream's result to rounding (its order
- * is the Blelloch tree of its own work-group size). No look-back, no polling. */
+ * is the Blelloch tree of its own work-group size). No look-back, no polling.
+ * The order is part of the contract (tests/fscan_model.py restates it in numpy and
+ * the GPU tests hold every result to it bit for bit): each element is converted by
+ * the C cast `(sum type) x` (round to nearest even, beyond the range an infinity);
+ * a tile is 256 threads x 16 consecutive elements, slots past numel count as +0; a
+ * thread adds its 16 left to right from +0; a wave's 64 thread sums are scanned by
+ * the shuffle tree (off = 1, 2, .. 32: lanes >= off add the value off lanes below);
+ * the four wave sums are added left to right, which gives each wave's base and the
+ * tile's total; a thread starts from (base + inclusive value of the lane below) +
+ * the tile's offset, never from `inclusive - own`, and emits the running value, then
+ * adds the element; the tile totals are scanned by the same procedure one level up
+ * (one tile / up to 4096 tiles / three levels). Every addition is an IEEE addition
+ * in the sum type: subnormals (half, float and double) are kept, -0 elements sum to
+ * +0, out[0] is +0, a NaN or inf - inf poisons exactly what lies behind it. */
 /* Every other pair of CloTypes upstream's generic kernel accepts (scan/clo_scan_abstract.c:122-125 pastes any two
  * type names): a half sum type, floating-point elements summed in an integer type (each element truncated by the
  * cast `(sum type) x`, as upstream's kernel does), integer sums narrower than the elements (the cast keeps the low

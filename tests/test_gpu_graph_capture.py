@@ -19,9 +19,9 @@ test_gpu_sort_by_key.order_key, oracle_lib.serial_scan, rbk_model, sbk_model, hi
 and oracle_lib.gselect.
 
 Two deliberate readings of the list of cases:
-- the typed (floating-point) scan is compared with an eager call on the same input, bit for bit, not with a float64
-  sum under a tolerance; one of its rounds uses small integers, whose float sums are exact, and is compared with
-  oracle_lib.serial_scan of the same integers as well;
+- the typed (floating-point) scan is compared with an eager call on the same input and with tests/fscan_model.py,
+  bit for bit, not with a float64 sum under a tolerance; one of its rounds uses small integers, whose float sums are
+  exact, and is compared with oracle_lib.serial_scan of the same integers as well;
 - oracle_lib.sbitonic restates upstream's network, which exists for powers of two only (for any other numel it would
   walk past the end of the array) and whose tie order the flip form behind clo_hip_bitonic_any does not keep. So the
   tie order against oracle_lib.sbitonic is checked where it is defined, clo_hip_bitonic_tiled with a key shift at 2^15,
@@ -625,8 +625,10 @@ def test_scan_in_chunks_with_device_carry_and_reduce_in_one_graph(dev, mem, et, 
 
 @pytest.mark.parametrize("et", ["float", "half"])
 def test_scan_exclusive_typed(dev, mem, et):
-    """Every replay is bit-equal to an eager call on the same input (the header: every addition in an order fixed by
-    the layout alone). The rounds of small integers have exact float sums: they equal the integer scan too."""
+    """Every replay is bit-equal to an eager call on the same input and to tests/fscan_model.py (the header: every
+    addition in an order fixed by the layout alone, the model restates which). The rounds of small integers have
+    exact float sums: they equal the integer scan too."""
+    import fscan_model
     lib = _lib()
     n = (1 << 16) + 5
     edt = np.dtype(_NP[et])
@@ -648,7 +650,10 @@ def test_scan_exclusive_typed(dev, mem, et):
         out_g.fill()
         out_e.fill()
         src.put(a)
-        return O.serial_scan(ints.astype(np.uint32), np.uint32).astype(np.float32) if kinds[k] == "small integers" else None
+        want = fscan_model.scan(a, np.float32)
+        if kinds[k] == "small integers":
+            same(want, O.serial_scan(ints.astype(np.uint32), np.uint32).astype(np.float32), "the model on small integers")
+        return want
 
     def verify(k, want):
         tag = "%s -> float round %d (%s)" % (et, k, kinds[k])
@@ -656,8 +661,7 @@ def test_scan_exclusive_typed(dev, mem, et):
         assert call(out_e) == 0 and lib.clo_hip_stream_synchronize(stream) == 0     # the eager call on the same input
         same(got, out_e.get(np.float32, n), tag + ": replay against eager")
         assert got[0] == 0.0 and not np.array_equal(got.view(np.uint8), canary(np.float32, n).view(np.uint8)), tag
-        if want is not None:
-            same(got, want, tag + ": exact sums")
+        same(got, want, tag + ": the model's sums" + (", which are exact" if kinds[k] == "small integers" else ""))
         same(src.get(edt, n), sent[k], tag + ": input")
 
     run_protocol(dev, Case(load, lambda: call(out_g), verify))

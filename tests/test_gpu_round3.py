@@ -554,9 +554,10 @@ def test_scan_into_narrower_or_integer_sums(gpu, types, n):
 @pytest.mark.parametrize("et", ["half", "uchar", "float"])
 def test_scan_with_half_sums(gpu, et):
     """A half sum type: every addition rounds to half precision (upstream: CLO_SCAN_SUM_TYPE half). Exact
-    while every partial sum is a small integer, within a few half-ulps of the running magnitude otherwise,
-    and the same bits from run to run."""
+    while every partial sum is a small integer, within a few half-ulps of the running magnitude otherwise
+    and there the bits of tests/fscan_model.py, and the same bits from run to run."""
     import cl_ops_amd as clo
+    import fscan_model
     ctx, q = gpu
     edt = clo.api.CLO_TYPE_NP[et]
     rng = np.random.default_rng(17)
@@ -570,9 +571,11 @@ def test_scan_with_half_sums(gpu, et):
     assert exact.max() < 2048 and np.array_equal(got.astype(np.float64), exact)
     if np.issubdtype(edt, np.floating):
         b = (rng.random(5000) * 0.5).astype(edt)
-        got = sc.with_host_data(b, q).astype(np.float64)
+        half = sc.with_host_data(b, q)
+        got = half.astype(np.float64)
         exact = np.concatenate(([0.0], np.cumsum(b.astype(np.float64))[:-1]))
         assert np.all(np.abs(got - exact) <= 64 * np.finfo(np.float16).eps * (exact + 1.0))
+        assert half.dtype == np.float16 and np.array_equal(half.view(np.uint8), fscan_model.scan(b, np.float16).view(np.uint8))
     sc.close()
 
 

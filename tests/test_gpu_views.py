@@ -362,8 +362,10 @@ def test_scan(dev, et, st, n):
 @pytest.mark.parametrize("et,st", [("float", "float"), ("half", "float"), ("double", "double")])
 @pytest.mark.parametrize("n", [100003, (1 << 21) + 5])
 def test_float_scan(dev, et, st, n):
-    """Floating-point sums: equal to the exact prefix sums to rounding, and bit-identical to the same scan on
-    256-byte aligned arrays (the order of the additions depends on the layout of the tiles alone)."""
+    """Floating-point sums: equal to the exact prefix sums to rounding (closeness to upstream), bit-identical to the
+    same scan on 256-byte aligned arrays, and that one bit-identical to tests/fscan_model.py (the order of the
+    additions depends on the layout of the tiles alone, and is the one the kernel file states)."""
+    import fscan_model
     clo, ctx, q = dev
     a = scan_input(et, n, 7)
     sdt = np.dtype(_NP[st])
@@ -380,6 +382,7 @@ def test_float_scan(dev, et, st, n):
         assert np.all(err <= 256 * eps), (tag, float(err.max() / eps))
         if aligned is None:
             aligned = got.copy()
+            assert np.array_equal(got.view(np.uint8), fscan_model.scan(a, sdt).view(np.uint8)), tag + ": differs from the model"
         assert np.array_equal(got.view(np.uint8), aligned.view(np.uint8)), tag + ": differs from the aligned scan"
 
     run_scan(dev, sc, a, sdt, [(0, 0)] + scan_configs(a.itemsize, sdt.itemsize, n < (1 << 21)), check)
