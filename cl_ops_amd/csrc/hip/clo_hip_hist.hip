@@ -22,6 +22,7 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
+#include "clo_hip_op_device.h"
 
 namespace {
 
@@ -32,7 +33,8 @@ constexpr int HIST_LDS_SPREAD = 32 * 1024; // the copies are spread over this mu
 constexpr int HIST_GROUPS_PER_CU = 4;
 
 enum { HIST_COPIES = 0, HIST_PEEL = 1, HIST_GLOBAL = 2 };
-// How a value becomes a number of the sum type, `(sum type) x` seen as bits (the pairs of clo_hip_rbk.hip):
+// How a value becomes a number of the sum type, `(sum type) x` seen as bits: the pairs of clo_op_cvt in a table of its
+// own, because a 64-bit sum is unsigned long long here (atomicAdd's type), not uint64_t:
 enum {
 	HIST_CVT_ONE32 = 0,   // values absent: every value is 1, 32-bit sum
 	HIST_CVT_ONE64 = 1,   // the same, 64-bit sum
@@ -235,21 +237,17 @@ int hist_dispatch(const hist_args& a, int cvt) {
 	}
 }
 
-// CloType numbers (clo_common.h): int 4, uint 5, long 6, ulong 7
-inline bool hist_int_type(int t) { return t >= 4 && t <= 7; }
-inline int hist_type_size(int t) { return t >= 6 ? 8 : 4; }
-
 // which conversion the kernels make, or -1: a pair of types this library does not sum
 int hist_cvt_of(bool vals, int value_type, int sum_type) {
-	if (!hist_int_type(sum_type)) return -1;
-	const int ss = hist_type_size(sum_type);
+	if (!clo_op_int_type(sum_type)) return -1;
+	const int ss = clo_op_type_size(sum_type);
 	if (!vals) return ss == 8 ? HIST_CVT_ONE64 : HIST_CVT_ONE32;
-	if (!hist_int_type(value_type)) return -1;
-	const int vs = hist_type_size(value_type);
+	if (!clo_op_int_type(value_type)) return -1;
+	const int vs = clo_op_type_size(value_type);
 	if (ss < vs) return -1;
 	if (ss == 4) return HIST_CVT_32;
 	if (vs == 8) return HIST_CVT_64;
-	return value_type == 4 ? HIST_CVT_S64 : HIST_CVT_U64;
+	return clo_op_type_signed(value_type) ? HIST_CVT_S64 : HIST_CVT_U64;
 }
 
 }  // namespace
@@ -257,8 +255,7 @@ int hist_cvt_of(bool vals, int value_type, int sum_type) {
 extern "C" {
 
 size_t clo_hip_histogram_tile(int key_size, int value_size) {
-	if (key_size != 1 && key_size != 2 && key_size != 4 && key_size != 8) return 0;
-	if (value_size != 0 && value_size != 4 && value_size != 8) return 0;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size)) return 0;
 	return hist_tile(key_size, value_size);
 }
 
@@ -278,14 +275,14 @@ int clo_hip_histogram(const void* keys_in, const void* values_in, void* hist_out
 	hipStream_t s = (hipStream_t) stream;
 	(void) workspace; (void) workspace_bytes;
 	if (!hist_out || num_bins == 0 || num_bins > 0xffffffffull || numel > 0xffffffffull) return CLO_HIP_EARGS;
-	if (key_size != 1 && key_size != 2 && key_size != 4 && key_size != 8) return CLO_HIP_EUNSUPPORTED;
+	if (!clo_op_key_size_ok(key_size)) return CLO_HIP_EUNSUPPORTED;
 	if (shift >= 8u * (unsigned) key_size) return CLO_HIP_EARGS;
 	const int cvt = hist_cvt_of(values_in != nullptr, value_type, sum_type);
 	if (cvt < 0) return CLO_HIP_EUNSUPPORTED;
-	const size_t ss = (size_t) hist_type_size(sum_type);
+	const size_t ss = (size_t) clo_op_type_size(sum_type);
 	if (clo_misaligned(hist_out, ss)) return CLO_HIP_EARGS;
 	if (numel > 0 && !keys_in) return CLO_HIP_EARGS;
-	if (clo_misaligned(keys_in, (size_t) key_size) || (values_in && clo_misaligned(values_in, (size_t) hist_type_size(value_type)))) return CLO_HIP_EARGS;
+	if (clo_misaligned(keys_in, (size_t) key_size) || (values_in && clo_misaligned(values_in, (size_t) clo_op_type_size(value_type)))) return CLO_HIP_EARGS;
 	if (!accumulate) {
 		const hipError_t e = hipMemsetAsync(hist_out, 0, num_bins * ss, s);
 		if (e != hipSuccess) return (int) e;
@@ -297,12 +294,7 @@ int clo_hip_histogram(const void* keys_in, const void* values_in, void* hist_out
 	a.max_groups = max_groups; a.s = s;
 	a.flip = key_signed ? 1ull << (8 * key_size - 1) : 0ull;
 	a.lower = lower;   // (the low key_size bytes: the value's two's complement for signed keys)
-	switch (key_size) {
-		case 1: return hist_dispatch<uint8_t>(a, cvt);
-		case 2: return hist_dispatch<uint16_t>(a, cvt);
-		case 4: return hist_dispatch<uint32_t>(a, cvt);
-		default: return hist_dispatch<uint64_t>(a, cvt);
-	}
+	return clo_op_by_key_size(key_size, [&](auto tk) { return hist_dispatch<decltype(tk)>(a, cvt); });
 }
 
 }  // extern "C"

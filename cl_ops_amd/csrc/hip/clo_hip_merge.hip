@@ -19,85 +19,25 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
+#include "clo_hip_op_device.h"
 
 namespace {
 
 constexpr int MERGE_THREADS = 256;
+static_assert(MERGE_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS");
 constexpr int merge_items(int key_size) { return key_size <= 2 ? 17 : 9; }
 constexpr size_t merge_tile(int key_size) { return (size_t) MERGE_THREADS * merge_items(key_size); }
 constexpr size_t MERGE_MIN_TILE = merge_tile(8);   // sizes the workspace, whose getter does not know the key size
 
-enum { MERGE_KEYS = 0, MERGE_V4 = 1, MERGE_V8 = 2, MERGE_ARG = 3 };
-template <int MODE> struct merge_val { typedef uint32_t T; };
-template <> struct merge_val<MERGE_V8> { typedef unsigned long long T; };
-
-__device__ __forceinline__ unsigned merge_min(unsigned a, unsigned b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned merge_max(unsigned a, unsigned b) { return a > b ? a : b; }
-
-// How many of the first d outputs of merging a[0, na) and b[0, nb) come from a, ties going to a. Whatever the arrays
-// hold, the result lies in [max(0, d - nb), min(d, na)] and only a[< na] and b[< nb] are read. XF: the keys are raw
-// and go through clo_keyx_fwd first.
-template <typename TK, bool XF>
-__device__ __forceinline__ unsigned merge_path(const TK* a, const TK* b, unsigned na, unsigned nb, unsigned d, const clo_keyx& kx) {
-	unsigned lo = d > nb ? d - nb : 0u, hi = merge_min(d, na);
-	while (lo < hi) {
-		const unsigned mid = lo + ((hi - lo) >> 1);
-		TK x = a[mid], y = b[d - 1u - mid];
-		if constexpr (XF) { x = clo_keyx_fwd<TK>(x, kx); y = clo_keyx_fwd<TK>(y, kx); }
-		if (x <= y) lo = mid + 1u; else hi = mid;
-	}
-	return lo;
-}
+// the modes CLO_OP_KEYS, V4, V8 and ARG (clo_hip_op_device.h); the table keeps a name of its own here because the
+// kernels' symbols spell it
+template <int MODE> struct merge_val : clo_op_val<MODE> {};
 
 template <typename TK>
 __global__ __launch_bounds__(MERGE_THREADS)
 void clo_merge_partition_kernel(const TK* __restrict__ ka, const TK* __restrict__ kb, unsigned na, unsigned nb, unsigned tiles,
 	clo_keyx kx, unsigned* __restrict__ split) {
-	const unsigned t = blockIdx.x * MERGE_THREADS + threadIdx.x;
-	if (t > tiles) return;
-	const unsigned long long n = (unsigned long long) na + nb, dd = (unsigned long long) t * merge_tile((int) sizeof(TK));
-	split[t] = merge_path<TK, true>(ka, kb, na, nb, (unsigned) (dd < n ? dd : n), kx);
-}
-
-// src[0, count) into dst[0, count) (LDS), lanes on adjacent 16-byte vectors from src's first 16-byte boundary on.
-template <typename T, bool XF>
-__device__ __forceinline__ void merge_stage(const T* __restrict__ src, unsigned count, T* dst, const clo_keyx& kx, unsigned tid) {
-	constexpr unsigned PER = 16u / sizeof(T);
-	typedef T vec __attribute__((ext_vector_type(PER)));
-	const unsigned head = merge_min((unsigned) ((16u - ((uintptr_t) src & 15u)) & 15u) / (unsigned) sizeof(T), count);
-	const unsigned nvec = (count - head) / PER, body_end = head + nvec * PER;
-	for (unsigned v = tid; v < nvec; v += MERGE_THREADS) {
-		const unsigned i0 = head + v * PER;
-		const vec x = *reinterpret_cast<const vec*>(src + i0);
-		#pragma unroll
-		for (unsigned c = 0; c < PER; ++c) dst[i0 + c] = XF ? clo_keyx_fwd<T>(x[c], kx) : x[c];
-	}
-	const unsigned rest = head + (count - body_end);   // fewer than 2 PER <= 32 elements
-	if (tid < rest) {
-		const unsigned i = tid < head ? tid : body_end + (tid - head);
-		dst[i] = XF ? clo_keyx_fwd<T>(src[i], kx) : src[i];
-	}
-}
-
-// dst[i] = get(i) for i in [0, count), the same division: 16-byte vector stores where dst allows them.
-template <typename T, typename F>
-__device__ __forceinline__ void merge_store(T* __restrict__ dst, unsigned count, unsigned tid, F get) {
-	constexpr unsigned PER = 16u / sizeof(T);
-	typedef T vec __attribute__((ext_vector_type(PER)));
-	const unsigned head = merge_min((unsigned) ((16u - ((uintptr_t) dst & 15u)) & 15u) / (unsigned) sizeof(T), count);
-	const unsigned nvec = (count - head) / PER, body_end = head + nvec * PER;
-	for (unsigned v = tid; v < nvec; v += MERGE_THREADS) {
-		const unsigned i0 = head + v * PER;
-		vec x;
-		#pragma unroll
-		for (unsigned c = 0; c < PER; ++c) x[c] = get(i0 + c);
-		*reinterpret_cast<vec*>(dst + i0) = x;
-	}
-	const unsigned rest = head + (count - body_end);
-	if (tid < rest) {
-		const unsigned i = tid < head ? tid : body_end + (tid - head);
-		dst[i] = get(i);
-	}
+	clo_op_partition<TK, merge_tile((int) sizeof(TK))>(ka, kb, na, nb, tiles, kx, split);
 }
 
 template <typename TK, int MODE>
@@ -108,37 +48,30 @@ void clo_merge_kernel(const TK* __restrict__ ka, const typename merge_val<MODE>:
 	typedef typename merge_val<MODE>::T TV;
 	constexpr int ITEMS = merge_items((int) sizeof(TK));
 	constexpr unsigned TILE = (unsigned) merge_tile((int) sizeof(TK));
-	constexpr bool VALS = MODE == MERGE_V4 || MODE == MERGE_V8;
+	constexpr bool VALS = MODE == CLO_OP_V4 || MODE == CLO_OP_V8;
 	static_assert(TILE <= 65536u, "slots are 16-bit");
 	__shared__ __attribute__((aligned(16))) TK s_keys[TILE];
-	__shared__ unsigned short s_slot[MODE == MERGE_KEYS ? 1 : TILE];
+	__shared__ unsigned short s_slot[MODE == CLO_OP_KEYS ? 1 : TILE];
 	__shared__ __attribute__((aligned(16))) TV s_vals[VALS ? TILE : 1];
 	const unsigned tid = threadIdx.x;
 
-	// the tile's outputs [d0, d1) and its ranges [a0, a1) of A and [b0, b1) of B. The searches' results are clamped to
-	// what d0, d1, na and nb alone allow: a0 in [d0 - nb, min(d0, na)], a1 - a0 in [0, d1 - d0], a1 in [d1 - nb, na].
-	// (Sorted inputs: the searches are monotone and nothing is changed.)
-	const unsigned long long n = (unsigned long long) na + nb, dd0 = (unsigned long long) blockIdx.x * TILE;
-	const unsigned d0 = (unsigned) (dd0 < n ? dd0 : n), d1 = (unsigned) (dd0 + TILE < n ? dd0 + TILE : n);
-	const unsigned cnt = d1 - d0;
-	unsigned a0 = split[blockIdx.x], a1 = split[blockIdx.x + 1u];
-	a0 = merge_min(merge_max(a0, d0 > nb ? d0 - nb : 0u), merge_min(d0, na));
-	a1 = merge_min(merge_max(a1, merge_max(a0, d1 > nb ? d1 - nb : 0u)), merge_min(na, a0 + cnt));
-	const unsigned b0 = d0 - a0, na_t = a1 - a0, nb_t = cnt - na_t;
+	// the tile's outputs [d0, d0 + cnt) and its ranges [a0, a0 + na_t) of A and [b0, b0 + nb_t) of B, the splits clamped
+	const clo_op_range r = clo_op_tile_range<TILE>(split, na, nb);
+	const unsigned d0 = r.d0, cnt = r.cnt, a0 = r.a0, b0 = r.b0, na_t = r.na_t, nb_t = r.nb_t;
 
-	merge_stage<TK, true>(ka + a0, na_t, s_keys, kx, tid);
-	merge_stage<TK, true>(kb + b0, nb_t, s_keys + na_t, kx, tid);
+	clo_op_stage<TK, true>(ka + a0, na_t, s_keys, kx, tid);
+	clo_op_stage<TK, true>(kb + b0, nb_t, s_keys + na_t, kx, tid);
 	if constexpr (VALS) {   // requested now, needed after the merge
-		merge_stage<TV, false>(va + a0, na_t, s_vals, kx, tid);
-		merge_stage<TV, false>(vb + b0, nb_t, s_vals + na_t, kx, tid);
+		clo_op_stage<TV, false>(va + a0, na_t, s_vals, kx, tid);
+		clo_op_stage<TV, false>(vb + b0, nb_t, s_vals + na_t, kx, tid);
 	}
 	__syncthreads();
 
 	// this thread's ITEMS outputs start at diagonal tid * ITEMS of the tile; past cnt nothing is valid and nothing is written
-	const unsigned diag = merge_min(tid * ITEMS, cnt);
-	unsigned ai = merge_path<TK, false>(s_keys, s_keys + na_t, na_t, nb_t, diag, kx);
+	const unsigned diag = clo_op_min(tid * ITEMS, cnt);
+	unsigned ai = clo_op_path<TK, false>(s_keys, s_keys + na_t, na_t, nb_t, diag, kx);
 	unsigned bi = diag - ai;
-	TK x = s_keys[merge_min(ai, TILE - 1u)], y = s_keys[merge_min(na_t + bi, TILE - 1u)];
+	TK x = s_keys[clo_op_min(ai, TILE - 1u)], y = s_keys[clo_op_min(na_t + bi, TILE - 1u)];
 	TK out[ITEMS];
 	unsigned slot[ITEMS];
 	#pragma unroll
@@ -148,7 +81,7 @@ void clo_merge_kernel(const TK* __restrict__ ka, const typename merge_val<MODE>:
 		out[i] = from_a ? x : y;
 		slot[i] = from_a ? ai : na_t + bi;
 		if (from_a) ++ai; else ++bi;
-		const TK next = s_keys[merge_min(from_a ? ai : na_t + bi, TILE - 1u)];
+		const TK next = s_keys[clo_op_min(from_a ? ai : na_t + bi, TILE - 1u)];
 		if (from_a) x = next; else y = next;
 	}
 	__syncthreads();   // every thread has read its keys: s_keys becomes the output tile
@@ -157,15 +90,15 @@ void clo_merge_kernel(const TK* __restrict__ ka, const typename merge_val<MODE>:
 		const unsigned j = tid * ITEMS + i;
 		if (j < cnt) {
 			s_keys[j] = clo_keyx_inv<TK>(out[i], kx);
-			if constexpr (MODE != MERGE_KEYS) s_slot[j] = (unsigned short) slot[i];   // < cnt
+			if constexpr (MODE != CLO_OP_KEYS) s_slot[j] = (unsigned short) slot[i];   // < cnt
 		}
 	}
 	__syncthreads();
-	if (kout) merge_store<TK>(kout + d0, cnt, tid, [&](unsigned j) { return s_keys[j]; });
-	if constexpr (VALS) merge_store<TV>(vout + d0, cnt, tid, [&](unsigned j) { return s_vals[s_slot[j]]; });
-	if constexpr (MODE == MERGE_ARG) {
+	if (kout) clo_op_store<TK>(kout + d0, cnt, tid, [&](unsigned j) { return s_keys[j]; });
+	if constexpr (VALS) clo_op_store<TV>(vout + d0, cnt, tid, [&](unsigned j) { return s_vals[s_slot[j]]; });
+	if constexpr (MODE == CLO_OP_ARG) {
 		const unsigned base_b = na + b0 - na_t;   // slot s >= na_t is B[b0 + s - na_t], index na + b0 + s - na_t of A || B (mod 2^32: exact)
-		merge_store<TV>(vout + d0, cnt, tid, [&](unsigned j) { const unsigned s = s_slot[j]; return s < na_t ? a0 + s : base_b + s; });
+		clo_op_store<TV>(vout + d0, cnt, tid, [&](unsigned j) { const unsigned s = s_slot[j]; return s < na_t ? a0 + s : base_b + s; });
 	}
 }
 
@@ -196,22 +129,19 @@ int merge_launch(const merge_args& a) {
 template <typename TK>
 int merge_dispatch(const merge_args& a, int mode) {
 	switch (mode) {
-		case MERGE_KEYS: return merge_launch<TK, MERGE_KEYS>(a);
-		case MERGE_V4: return merge_launch<TK, MERGE_V4>(a);
-		case MERGE_V8: return merge_launch<TK, MERGE_V8>(a);
-		default: return merge_launch<TK, MERGE_ARG>(a);
+		case CLO_OP_KEYS: return merge_launch<TK, CLO_OP_KEYS>(a);
+		case CLO_OP_V4: return merge_launch<TK, CLO_OP_V4>(a);
+		case CLO_OP_V8: return merge_launch<TK, CLO_OP_V8>(a);
+		default: return merge_launch<TK, CLO_OP_ARG>(a);
 	}
 }
-
-inline bool merge_key_size_ok(int ks) { return ks == 1 || ks == 2 || ks == 4 || ks == 8; }
-inline bool merge_value_size_ok(int vs) { return vs == 0 || vs == 4 || vs == 8; }
 
 }  // namespace
 
 extern "C" {
 
 size_t clo_hip_merge_tile(int key_size, int value_size) {
-	if (!merge_key_size_ok(key_size) || !merge_value_size_ok(value_size)) return 0;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size)) return 0;
 	return merge_tile(key_size);
 }
 
@@ -219,14 +149,13 @@ size_t clo_hip_merge_workspace_bytes(size_t numel_a, size_t numel_b) {
 	const size_t n = numel_a + numel_b;
 	if (n == 0 || n < numel_a) return 0;
 	// tiles + 1 split points of 4 bytes for the smallest tile, in whole CLO_HIP_WORKSPACE_ALIGN units
-	const size_t bytes = ((n + MERGE_MIN_TILE - 1) / MERGE_MIN_TILE + 1) * sizeof(unsigned);
-	return (bytes + CLO_HIP_WORKSPACE_ALIGN - 1) / CLO_HIP_WORKSPACE_ALIGN * CLO_HIP_WORKSPACE_ALIGN;
+	return clo_op_ws_align(((n + MERGE_MIN_TILE - 1) / MERGE_MIN_TILE + 1) * sizeof(unsigned));
 }
 
 int clo_hip_merge(const void* keys_a, const void* values_a, size_t numel_a, const void* keys_b, const void* values_b, size_t numel_b,
 	void* keys_out, void* values_out, int key_size, int key_kind, int value_size, void* workspace, size_t workspace_bytes, void* stream) {
 	if (key_kind < 0 || key_kind > 2) return CLO_HIP_EARGS;
-	if (!merge_key_size_ok(key_size) || !merge_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
 	if (numel_a > 0xffffffffull || numel_b > 0xffffffffull || numel_a + numel_b > 0xffffffffull) return CLO_HIP_EARGS;
 	if ((numel_a > 0 && !keys_a) || (numel_b > 0 && !keys_b)) return CLO_HIP_EARGS;
 	if (!keys_out && !values_out) return CLO_HIP_EARGS;
@@ -252,13 +181,8 @@ int clo_hip_merge(const void* keys_a, const void* values_a, size_t numel_a, cons
 	a.na = (unsigned) numel_a; a.nb = (unsigned) numel_b;
 	a.kx = clo_keyx_make(key_kind, 0, 8 * key_size);
 	a.split = (unsigned*) workspace; a.s = (hipStream_t) stream;
-	const int mode = value_size == 0 ? MERGE_KEYS : arg ? MERGE_ARG : value_size == 4 ? MERGE_V4 : MERGE_V8;
-	switch (key_size) {
-		case 1: return merge_dispatch<uint8_t>(a, mode);
-		case 2: return merge_dispatch<uint16_t>(a, mode);
-		case 4: return merge_dispatch<uint32_t>(a, mode);
-		default: return merge_dispatch<uint64_t>(a, mode);
-	}
+	const int mode = clo_op_mode(value_size, arg);
+	return clo_op_by_key_size(key_size, [&](auto tk) { return merge_dispatch<decltype(tk)>(a, mode); });
 }
 
 }  // extern "C"

@@ -15,18 +15,18 @@
 //   3. apply sweep  a group reads its tile again, runs the same segmented scan over it starting from the tile's
 //                   incoming state, and stores EVERY element: the state before the element's own step (the identity
 //                   where the element is a head) for the exclusive form, after it for the inclusive form.
-// This file carries its own copies of the helpers and of the first two kernels of clo_hip_rbk.hip (which stays as it
-// is): here there is always an aggregate, the "next element is a head" bit and the run count are not needed, and
-// values / out carry no __restrict__, because out may be values_in itself (element i's result lands at index i, and
-// a thread has loaded its elements of the tile before it stores any).
+// The segmented scan itself — the operator, the wave scan and the scan of a tile's pieces — is shared with reduce by
+// key (clo_hip_op_device.h) and used here with an aggregate always (AGG = true). What differs here on purpose: loads
+// and stores count inside the tile in 32 bits, the "next element is a head" bit and the run count are not needed,
+// advance() is branch-free, and values / out carry no __restrict__, because out may be values_in itself (element i's
+// result lands at index i, and a thread has loaded its elements of the tile before it stores any).
 // A tile is 256 threads x 4 consecutive elements x ROWS rows; inside a tile the order is row, wave, lane, element.
 // min / max are computed on unsigned numbers: a signed sum type has its sign bit flipped on load and on store.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
+#include "clo_hip_op_device.h"
 
 namespace {
 
@@ -34,120 +34,11 @@ constexpr int SBK_THREADS = 256;
 constexpr int SBK_WAVES = SBK_THREADS / 64;
 constexpr int SBK_VEC = 4;
 constexpr int SBK_ROW_ELEMS = SBK_THREADS * SBK_VEC;   // 1024
+static_assert(SBK_THREADS == CLO_OP_THREADS && SBK_VEC == CLO_OP_VEC, "the shared helpers' work-group and vector");
 
-// rows per tile: the rule of reduce by key (256 bytes of keys and values per thread at most)
-constexpr int sbk_rows(int key_size, int value_size) { return key_size + value_size <= 8 ? 8 : 4; }
-
-enum { SBK_SUM = 0, SBK_MIN = 1, SBK_MAX = 2 };
-// How a value becomes a number of the sum type, `(sum type) x` seen as bits:
-enum {
-	SBK_CVT_32 = 0,      // 32-bit value, 32-bit sum
-	SBK_CVT_S64 = 1,     // int value, 64-bit sum (sign extension)
-	SBK_CVT_U64 = 2,     // uint value, 64-bit sum
-	SBK_CVT_64 = 3,      // 64-bit value, 64-bit sum
-	SBK_CVT_ONE32 = 4,   // values absent: every value is 1, 32-bit sum
-	SBK_CVT_ONE64 = 5    // the same, 64-bit sum
-};
-template <int CVT> struct sbk_cvt;
-template <> struct sbk_cvt<SBK_CVT_32> { typedef uint32_t TV; typedef uint32_t TS; static constexpr int vs = 4; };
-template <> struct sbk_cvt<SBK_CVT_S64> { typedef int32_t TV; typedef uint64_t TS; static constexpr int vs = 4; };
-template <> struct sbk_cvt<SBK_CVT_U64> { typedef uint32_t TV; typedef uint64_t TS; static constexpr int vs = 4; };
-template <> struct sbk_cvt<SBK_CVT_64> { typedef uint64_t TV; typedef uint64_t TS; static constexpr int vs = 8; };
-template <> struct sbk_cvt<SBK_CVT_ONE32> { typedef uint32_t TV; typedef uint32_t TS; static constexpr int vs = 0; };
-template <> struct sbk_cvt<SBK_CVT_ONE64> { typedef uint32_t TV; typedef uint64_t TS; static constexpr int vs = 0; };
-
-template <int OP, typename TS>
-__device__ __forceinline__ constexpr TS sbk_identity() { return OP == SBK_MIN ? (TS) ~(TS) 0 : (TS) 0; }
-template <int OP, typename TS>
-__device__ __forceinline__ TS sbk_op(TS a, TS b) {
-	if constexpr (OP == SBK_SUM) return (TS) (a + b);
-	else if constexpr (OP == SBK_MIN) return a < b ? a : b;
-	else return a > b ? a : b;
-}
-
-// The state of a stretch of elements: the heads in it, and the aggregate from its last head (from its start
-// when it has none) to its end.
-template <typename TS>
-struct sbk_state { unsigned h; TS a; };
-
-template <int OP, typename TS>
-__device__ __forceinline__ sbk_state<TS> sbk_combine(const sbk_state<TS>& l, const sbk_state<TS>& r) {
-	sbk_state<TS> o;
-	o.h = l.h + r.h;
-	o.a = r.h ? r.a : sbk_op<OP, TS>(l.a, r.a);
-	return o;
-}
-template <int OP, typename TS>
-__device__ __forceinline__ sbk_state<TS> sbk_empty() { sbk_state<TS> o; o.h = 0; o.a = sbk_identity<OP, TS>(); return o; }
-
-// One DPP move of a 32- or 64-bit integer; a lane without a source (and every lane of a row the mask leaves out)
-// gets `old`.
-template <int CTRL, int ROW_MASK, typename T>
-__device__ __forceinline__ T sbk_dpp(T old, T x) {
-	static_assert(std::is_integral<T>::value && (sizeof(T) == 4 || sizeof(T) == 8), "32- or 64-bit integers");
-	if constexpr (sizeof(T) == 4) {
-		return (T) (unsigned) __builtin_amdgcn_update_dpp((int) old, (int) x, CTRL, ROW_MASK, 0xF, false);
-	} else {
-		const unsigned long long o = (unsigned long long) old, v = (unsigned long long) x;
-		const unsigned lo = (unsigned) __builtin_amdgcn_update_dpp((int) (unsigned) o, (int) (unsigned) v, CTRL, ROW_MASK, 0xF, false);
-		const unsigned hi = (unsigned) __builtin_amdgcn_update_dpp((int) (unsigned) (o >> 32), (int) (unsigned) (v >> 32), CTRL, ROW_MASK, 0xF, false);
-		return (T) (((unsigned long long) hi << 32) | lo);
-	}
-}
-
-template <int OP, int CTRL, int ROW_MASK, typename TS>
-__device__ __forceinline__ void sbk_seg_step(sbk_state<TS>& s) {
-	sbk_state<TS> l;
-	l.h = sbk_dpp<CTRL, ROW_MASK, unsigned>(0u, s.h);
-	l.a = sbk_dpp<CTRL, ROW_MASK, TS>(sbk_identity<OP, TS>(), s.a);
-	s = sbk_combine<OP, TS>(l, s);
-}
-
-// Inclusive segmented scan of the 64 lane states of a whole wave: the network of clo_wave_scan_inclusive
-// (clo_hip_internal.h) with the operator above.
-template <int OP, typename TS>
-__device__ __forceinline__ sbk_state<TS> sbk_wave_scan(sbk_state<TS> s) {
-	sbk_seg_step<OP, 0x111, 0xF, TS>(s);   // row_shr:1
-	sbk_seg_step<OP, 0x112, 0xF, TS>(s);   // row_shr:2
-	sbk_seg_step<OP, 0x114, 0xF, TS>(s);   // row_shr:4
-	sbk_seg_step<OP, 0x118, 0xF, TS>(s);   // row_shr:8
-	sbk_seg_step<OP, 0x142, 0xA, TS>(s);   // row_bcast:15 into rows 1 and 3
-	sbk_seg_step<OP, 0x143, 0xC, TS>(s);   // row_bcast:31 into rows 2 and 3
-	return s;
-}
-
-template <typename T>
-__device__ __forceinline__ T sbk_shfl(T v, int src_lane) {
-	if constexpr (sizeof(T) == 8) {
-		const unsigned long long b = (unsigned long long) v;
-		const unsigned lo = (unsigned) __shfl((int) (unsigned) b, src_lane, 64);
-		const unsigned hi = (unsigned) __shfl((int) (unsigned) (b >> 32), src_lane, 64);
-		return (T) (((unsigned long long) hi << 32) | lo);
-	} else {
-		return (T) (unsigned) __shfl((int) (unsigned) v, src_lane, 64);
-	}
-}
-
-// the state of the lanes before this one: the inclusive scan moved up one lane
-template <int OP, typename TS>
-__device__ __forceinline__ sbk_state<TS> sbk_wave_exclusive(const sbk_state<TS>& incl, unsigned lane) {
-	sbk_state<TS> e;
-	e.h = sbk_shfl<unsigned>(incl.h, (int) lane - 1);
-	e.a = sbk_shfl<TS>(incl.a, (int) lane - 1);
-	return lane == 0 ? sbk_empty<OP, TS>() : e;
-}
-
-template <typename T>
-__device__ __forceinline__ T sbk_readlane(T v, unsigned lane) {   // `lane` is wave-uniform
-	if constexpr (sizeof(T) == 8) {
-		const unsigned long long b = (unsigned long long) v;
-		const unsigned lo = (unsigned) __builtin_amdgcn_readlane((int) (unsigned) b, (int) lane);
-		const unsigned hi = (unsigned) __builtin_amdgcn_readlane((int) (unsigned) (b >> 32), (int) lane);
-		return (T) (((unsigned long long) hi << 32) | lo);
-	} else {
-		return (T) (unsigned) __builtin_amdgcn_readlane((int) (unsigned) v, (int) lane);
-	}
-}
+// the conversions CLO_OP_CVT_* (clo_hip_op_device.h); the table keeps a name of its own here because the kernels'
+// symbols spell it
+template <int CVT> struct sbk_cvt : clo_op_cvt<CVT> {};
 
 // Where a lane's elements lie is counted inside the TILE, in 32 bits: `t` points to the tile's first element, `off`
 // (a multiple of 4) is the lane's first element of a row in the tile, and `lim` the number of elements the tile has
@@ -201,7 +92,7 @@ struct sbk_row {
 	// `first`: the tile is the array's first (its element 0 has no left neighbour and is a head)
 	static __device__ __forceinline__ unsigned heads(const TK* __restrict__ t, const TK (&k)[SBK_VEC], unsigned off, unsigned lim, bool first, unsigned lane) {
 		// the key before the lane's first: the lane below has it, lane 0 reads it (the tile's first element: across the tile edge)
-		TK prev = sbk_shfl<TK>(k[SBK_VEC - 1], (int) lane - 1);
+		TK prev = clo_op_shfl<TK>(k[SBK_VEC - 1], (int) lane - 1);
 		const bool start = first && off == 0;
 		if (lane == 0 && !start && off < lim) prev = t[(ptrdiff_t) off - 1];
 		unsigned hb = 0;
@@ -213,38 +104,22 @@ struct sbk_row {
 
 	static __device__ __forceinline__ TS value(const TV (&v)[SBK_VEC], int c, TS flip) {
 		if constexpr (!VALS) return (TS) 1;
-		else if constexpr (OP == SBK_SUM) return (TS) v[c];
+		else if constexpr (OP == CLO_OP_SUM) return (TS) v[c];
 		else return (TS) ((TS) v[c] ^ flip);
 	}
 
 	// `s` continued over element c of the lane's four; returns what the run had gathered BEFORE the element: the
 	// identity where the element is a head. Without a branch or a lane mask: the head bit, spread over the word,
 	// clears the aggregate (sets it for min, whose identity is all ones).
-	static __device__ __forceinline__ TS advance(sbk_state<TS>& s, unsigned hb, const TV (&v)[SBK_VEC], int c, TS flip) {
+	static __device__ __forceinline__ TS advance(clo_op_seg_state<TS>& s, unsigned hb, const TV (&v)[SBK_VEC], int c, TS flip) {
 		const unsigned head = (hb >> c) & 1u;
 		const TS spread = (TS) 0 - (TS) head;
-		const TS before = OP == SBK_MIN ? (TS) (s.a | spread) : (TS) (s.a & ~spread);
-		s.a = sbk_op<OP, TS>(before, value(v, c, flip));
+		const TS before = OP == CLO_OP_MIN ? (TS) (s.a | spread) : (TS) (s.a & ~spread);
+		s.a = clo_op_seg_op<OP, TS>(before, value(v, c, flip));
 		s.h += head;
 		return before;
 	}
 };
-
-// The pieces of a tile (ROWS x SBK_WAVES wave totals, in LDS, written before the tile's barrier): every wave scans
-// them for itself; piece p's exclusive state comes back for p = row * SBK_WAVES + wave.
-template <int OP, typename TS, int PIECES>
-__device__ __forceinline__ sbk_state<TS> sbk_scan_pieces(const unsigned* s_h, const TS* s_a, unsigned lane, sbk_state<TS>* total) {
-	static_assert(PIECES <= 64, "one piece per lane");
-	sbk_state<TS> p = sbk_empty<OP, TS>();
-	if (lane < (unsigned) PIECES) {
-		p.h = s_h[lane];
-		p.a = s_a[lane];
-	}
-	const sbk_state<TS> incl = sbk_wave_scan<OP, TS>(p);
-	total->h = sbk_readlane<unsigned>(incl.h, 63u);
-	total->a = sbk_readlane<TS>(incl.a, 63u);
-	return sbk_wave_exclusive<OP, TS>(incl, lane);
-}
 
 // ---- 1. tile sweep ----
 template <typename TK, int CVT, int OP, int ROWS>
@@ -274,10 +149,10 @@ void clo_sbk_sweep_kernel(const TK* __restrict__ keys, const typename sbk_cvt<CV
 	#pragma unroll
 	for (int r = 0; r < ROWS; ++r) {
 		const unsigned hb = R::heads(tk, k[r], tid * SBK_VEC + r * SBK_ROW_ELEMS, lim, blockIdx.x == 0, lane);
-		sbk_state<TS> s = sbk_empty<OP, TS>();
+		clo_op_seg_state<TS> s = clo_op_seg_empty<OP, TS>();
 		#pragma unroll
 		for (int c = 0; c < SBK_VEC; ++c) R::advance(s, hb, v[r], c, flip);
-		s = sbk_wave_scan<OP, TS>(s);
+		s = clo_op_seg_wave_scan<OP, true, TS>(s);
 		if (lane == 63) {
 			s_h[r * SBK_WAVES + wave] = s.h;
 			s_a[r * SBK_WAVES + wave] = s.a;
@@ -285,8 +160,8 @@ void clo_sbk_sweep_kernel(const TK* __restrict__ keys, const typename sbk_cvt<CV
 	}
 	__syncthreads();
 	if (wave == 0) {
-		sbk_state<TS> total;
-		(void) sbk_scan_pieces<OP, TS, PIECES>(s_h, s_a, lane, &total);
+		clo_op_seg_state<TS> total;
+		(void) clo_op_seg_scan_pieces<OP, true, TS, PIECES>(s_h, s_a, lane, &total);
 		if (lane == 0) {
 			tile_h[blockIdx.x] = total.h;
 			tile_a[blockIdx.x] = total.a;
@@ -294,7 +169,8 @@ void clo_sbk_sweep_kernel(const TK* __restrict__ keys, const typename sbk_cvt<CV
 	}
 }
 
-// ---- 2. state scan: one group; tile t gets the state of the tiles before it, in place ----
+// ---- 2. state scan: one group; tile t gets the state of the tiles before it, in place. (clo_rbk_states_kernel's body
+// with AGG = true and no run count; as one shared function both compiled to other instructions, so each file keeps its own.) ----
 template <int CVT, int OP>
 __global__ __launch_bounds__(SBK_THREADS)
 void clo_sbk_states_kernel(unsigned* __restrict__ tile_h, typename sbk_cvt<CVT>::TS* __restrict__ tile_a, unsigned tiles) {
@@ -303,43 +179,43 @@ void clo_sbk_states_kernel(unsigned* __restrict__ tile_h, typename sbk_cvt<CVT>:
 	__shared__ unsigned s_h[SBK_WAVES];
 	__shared__ TS s_a[SBK_WAVES];
 	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	sbk_state<TS> running = sbk_empty<OP, TS>();   // the state of everything before this chunk (the same in every thread)
+	clo_op_seg_state<TS> running = clo_op_seg_empty<OP, TS>();   // the state of everything before this chunk (the same in every thread)
 	for (unsigned chunk = 0; chunk < tiles; chunk += SBK_THREADS * PER) {
 		const unsigned t0 = chunk + tid * PER;
-		sbk_state<TS> st[PER];
-		sbk_state<TS> mine = sbk_empty<OP, TS>();
+		clo_op_seg_state<TS> st[PER];
+		clo_op_seg_state<TS> mine = clo_op_seg_empty<OP, TS>();
 		#pragma unroll
 		for (int j = 0; j < PER; ++j) {
-			st[j] = sbk_empty<OP, TS>();
+			st[j] = clo_op_seg_empty<OP, TS>();
 			if (t0 + j < tiles) {
 				st[j].h = tile_h[t0 + j];
 				st[j].a = tile_a[t0 + j];
 			}
-			mine = sbk_combine<OP, TS>(mine, st[j]);
+			mine = clo_op_seg_combine<OP, true, TS>(mine, st[j]);
 		}
-		const sbk_state<TS> incl = sbk_wave_scan<OP, TS>(mine);
+		const clo_op_seg_state<TS> incl = clo_op_seg_wave_scan<OP, true, TS>(mine);
 		if (lane == 63) {
 			s_h[wave] = incl.h;
 			s_a[wave] = incl.a;
 		}
 		__syncthreads();
-		sbk_state<TS> before = running, all = running;
+		clo_op_seg_state<TS> before = running, all = running;
 		#pragma unroll
 		for (unsigned w = 0; w < (unsigned) SBK_WAVES; ++w) {
-			sbk_state<TS> p;
+			clo_op_seg_state<TS> p;
 			p.h = s_h[w];
 			p.a = s_a[w];
-			if (w < wave) before = sbk_combine<OP, TS>(before, p);
-			all = sbk_combine<OP, TS>(all, p);
+			if (w < wave) before = clo_op_seg_combine<OP, true, TS>(before, p);
+			all = clo_op_seg_combine<OP, true, TS>(all, p);
 		}
-		sbk_state<TS> s = sbk_combine<OP, TS>(before, sbk_wave_exclusive<OP, TS>(incl, lane));
+		clo_op_seg_state<TS> s = clo_op_seg_combine<OP, true, TS>(before, clo_op_seg_wave_exclusive<OP, true, TS>(incl, lane));
 		#pragma unroll
 		for (int j = 0; j < PER; ++j) {
 			if (t0 + j < tiles) {
 				tile_h[t0 + j] = s.h;
 				tile_a[t0 + j] = s.a;
 			}
-			s = sbk_combine<OP, TS>(s, st[j]);
+			s = clo_op_seg_combine<OP, true, TS>(s, st[j]);
 		}
 		running = all;
 		__syncthreads();   // s_h / s_a are written again in the next chunk
@@ -368,7 +244,7 @@ void clo_sbk_apply_kernel(const TK* __restrict__ keys, const typename sbk_cvt<CV
 
 	TV v[ROWS][SBK_VEC];
 	unsigned hb[ROWS];
-	sbk_state<TS> ex[ROWS];   // the lanes of this wave before this one, per row
+	clo_op_seg_state<TS> ex[ROWS];   // the lanes of this wave before this one, per row
 	{
 		TK k[ROWS][SBK_VEC];   // dead once the head bits are known
 		#pragma unroll
@@ -379,19 +255,19 @@ void clo_sbk_apply_kernel(const TK* __restrict__ keys, const typename sbk_cvt<CV
 		#pragma unroll
 		for (int r = 0; r < ROWS; ++r) {
 			hb[r] = R::heads(tk, k[r], tid * SBK_VEC + r * SBK_ROW_ELEMS, lim, blockIdx.x == 0, lane);
-			sbk_state<TS> s = sbk_empty<OP, TS>();
+			clo_op_seg_state<TS> s = clo_op_seg_empty<OP, TS>();
 			#pragma unroll
 			for (int c = 0; c < SBK_VEC; ++c) R::advance(s, hb[r], v[r], c, flip);
-			s = sbk_wave_scan<OP, TS>(s);
+			s = clo_op_seg_wave_scan<OP, true, TS>(s);
 			if (lane == 63) {
 				s_h[r * SBK_WAVES + wave] = s.h;
 				s_a[r * SBK_WAVES + wave] = s.a;
 			}
-			ex[r] = sbk_wave_exclusive<OP, TS>(s, lane);
+			ex[r] = clo_op_seg_wave_exclusive<OP, true, TS>(s, lane);
 		}
 	}
 	// the carry into the tile: the open run's aggregate so far (its head count does not matter here)
-	sbk_state<TS> tile_in;
+	clo_op_seg_state<TS> tile_in;
 	tile_in.h = 0;
 	tile_in.a = tile_a[blockIdx.x];
 	__syncthreads();   // every thread of the group has loaded its elements: from here on `out` may be written over `values`
@@ -400,20 +276,20 @@ void clo_sbk_apply_kernel(const TK* __restrict__ keys, const typename sbk_cvt<CV
 	// compiler's report); behind this empty statement it forms them again, one 32-bit compare each.
 	unsigned lim2 = lim;
 	asm volatile("" : "+s"(lim2));
-	sbk_state<TS> total;
-	const sbk_state<TS> pieces = sbk_scan_pieces<OP, TS, PIECES>(s_h, s_a, lane, &total);
+	clo_op_seg_state<TS> total;
+	const clo_op_seg_state<TS> pieces = clo_op_seg_scan_pieces<OP, true, TS, PIECES>(s_h, s_a, lane, &total);
 	#pragma unroll
 	for (int r = 0; r < ROWS; ++r) {
-		sbk_state<TS> before;   // the pieces before this wave's piece of row r
-		before.h = sbk_readlane<unsigned>(pieces.h, (unsigned) r * SBK_WAVES + wave);
-		before.a = sbk_readlane<TS>(pieces.a, (unsigned) r * SBK_WAVES + wave);
-		sbk_state<TS> s = sbk_combine<OP, TS>(sbk_combine<OP, TS>(tile_in, before), ex[r]);
+		clo_op_seg_state<TS> before;   // the pieces before this wave's piece of row r
+		before.h = clo_op_readlane<unsigned>(pieces.h, (unsigned) r * SBK_WAVES + wave);
+		before.a = clo_op_readlane<TS>(pieces.a, (unsigned) r * SBK_WAVES + wave);
+		clo_op_seg_state<TS> s = clo_op_seg_combine<OP, true, TS>(clo_op_seg_combine<OP, true, TS>(tile_in, before), ex[r]);
 		TS res[SBK_VEC];
 		#pragma unroll
 		for (int c = 0; c < SBK_VEC; ++c) {
 			const TS excl = R::advance(s, hb[r], v[r], c, flip);   // the identity where the element starts a run
 			const TS x = inclusive ? s.a : excl;
-			res[c] = OP == SBK_SUM ? x : (TS) (x ^ flip);
+			res[c] = OP == CLO_OP_SUM ? x : (TS) (x ^ flip);
 		}
 		sbk_store4<TS>(out + tile_base, tid * SBK_VEC + r * SBK_ROW_ELEMS, lim2, ovec != 0, res);
 	}
@@ -424,19 +300,15 @@ struct sbk_args {
 	size_t n; unsigned long long flip; int inclusive; void* ws; hipStream_t s;
 };
 
-inline size_t sbk_align(size_t x) { return (x + CLO_HIP_WORKSPACE_ALIGN - 1) / CLO_HIP_WORKSPACE_ALIGN * CLO_HIP_WORKSPACE_ALIGN; }
-constexpr size_t SBK_MIN_TILE = (size_t) SBK_ROW_ELEMS * 4;
-inline size_t sbk_max_tiles(size_t numel) { return (numel + SBK_MIN_TILE - 1) / SBK_MIN_TILE + 1; }
-
 template <typename TK, int CVT, int OP>
 int sbk_launch(const sbk_args& a) {
 	typedef typename sbk_cvt<CVT>::TV TV;
 	typedef typename sbk_cvt<CVT>::TS TS;
-	constexpr int ROWS = sbk_rows((int) sizeof(TK), sbk_cvt<CVT>::vs);
+	constexpr int ROWS = clo_op_seg_rows((int) sizeof(TK), sbk_cvt<CVT>::vs);
 	const size_t tile = (size_t) ROWS * SBK_ROW_ELEMS;
 	const unsigned tiles = (unsigned) ((a.n + tile - 1) / tile);
 	unsigned* tile_h = (unsigned*) a.ws;
-	TS* tile_a = (TS*) ((char*) a.ws + sbk_align(sbk_max_tiles(a.n) * sizeof(unsigned)));
+	TS* tile_a = (TS*) ((char*) a.ws + clo_op_ws_align(clo_op_seg_max_tiles(a.n) * sizeof(unsigned)));
 	const int kvec = (uintptr_t) a.keys_in % (SBK_VEC * sizeof(TK)) == 0;
 	const int vvec = (uintptr_t) a.values_in % (SBK_VEC * sizeof(TV)) == 0;
 	const int ovec = (uintptr_t) a.out % 16 == 0;
@@ -460,13 +332,13 @@ int sbk_launch(const sbk_args& a) {
 
 template <typename TK, int CVT>
 int sbk_dispatch_op(const sbk_args& a, int op) {
-	if constexpr (CVT == SBK_CVT_ONE32 || CVT == SBK_CVT_ONE64) {
-		return sbk_launch<TK, CVT, SBK_SUM>(a);   // (no values: min / max were refused)
+	if constexpr (CVT == CLO_OP_CVT_ONE32 || CVT == CLO_OP_CVT_ONE64) {
+		return sbk_launch<TK, CVT, CLO_OP_SUM>(a);   // (no values: min / max were refused)
 	} else {
 		switch (op) {
-			case SBK_SUM: return sbk_launch<TK, CVT, SBK_SUM>(a);
-			case SBK_MIN: return sbk_launch<TK, CVT, SBK_MIN>(a);
-			case SBK_MAX: return sbk_launch<TK, CVT, SBK_MAX>(a);
+			case CLO_OP_SUM: return sbk_launch<TK, CVT, CLO_OP_SUM>(a);
+			case CLO_OP_MIN: return sbk_launch<TK, CVT, CLO_OP_MIN>(a);
+			case CLO_OP_MAX: return sbk_launch<TK, CVT, CLO_OP_MAX>(a);
 			default: return CLO_HIP_EARGS;
 		}
 	}
@@ -475,32 +347,14 @@ int sbk_dispatch_op(const sbk_args& a, int op) {
 template <typename TK>
 int sbk_dispatch_cvt(const sbk_args& a, int cvt, int op) {
 	switch (cvt) {
-		case SBK_CVT_32: return sbk_dispatch_op<TK, SBK_CVT_32>(a, op);
-		case SBK_CVT_S64: return sbk_dispatch_op<TK, SBK_CVT_S64>(a, op);
-		case SBK_CVT_U64: return sbk_dispatch_op<TK, SBK_CVT_U64>(a, op);
-		case SBK_CVT_64: return sbk_dispatch_op<TK, SBK_CVT_64>(a, op);
-		case SBK_CVT_ONE32: return sbk_dispatch_op<TK, SBK_CVT_ONE32>(a, op);
-		case SBK_CVT_ONE64: return sbk_dispatch_op<TK, SBK_CVT_ONE64>(a, op);
-		default: return CLO_HIP_EUNSUPPORTED;
+		case CLO_OP_CVT_32: return sbk_dispatch_op<TK, CLO_OP_CVT_32>(a, op);
+		case CLO_OP_CVT_S64: return sbk_dispatch_op<TK, CLO_OP_CVT_S64>(a, op);
+		case CLO_OP_CVT_U64: return sbk_dispatch_op<TK, CLO_OP_CVT_U64>(a, op);
+		case CLO_OP_CVT_64: return sbk_dispatch_op<TK, CLO_OP_CVT_64>(a, op);
+		case CLO_OP_CVT_ONE32: return sbk_dispatch_op<TK, CLO_OP_CVT_ONE32>(a, op);
+		case CLO_OP_CVT_ONE64: return sbk_dispatch_op<TK, CLO_OP_CVT_ONE64>(a, op);
+		default: return CLO_HIP_EUNSUPPORTED;   // (CLO_OP_CVT_NONE too: a scan always has an aggregate)
 	}
-}
-
-// CloType numbers (clo_common.h): int 4, uint 5, long 6, ulong 7
-inline bool sbk_int_type(int t) { return t >= 4 && t <= 7; }
-inline int sbk_type_size(int t) { return t >= 6 ? 8 : 4; }
-inline bool sbk_type_signed(int t) { return t == 4 || t == 6; }
-
-// which conversion the kernels make, or -1: a pair of types this library does not scan
-int sbk_cvt_of(bool vals, int value_type, int sum_type) {
-	if (!sbk_int_type(sum_type)) return -1;
-	const int ss = sbk_type_size(sum_type);
-	if (!vals) return ss == 8 ? SBK_CVT_ONE64 : SBK_CVT_ONE32;
-	if (!sbk_int_type(value_type)) return -1;
-	const int vs = sbk_type_size(value_type);
-	if (ss < vs) return -1;
-	if (ss == 4) return SBK_CVT_32;
-	if (vs == 8) return SBK_CVT_64;
-	return sbk_type_signed(value_type) ? SBK_CVT_S64 : SBK_CVT_U64;
 }
 
 }  // namespace
@@ -508,43 +362,34 @@ int sbk_cvt_of(bool vals, int value_type, int sum_type) {
 extern "C" {
 
 size_t clo_hip_scan_by_key_tile(int key_size, int value_size) {
-	if (key_size != 1 && key_size != 2 && key_size != 4 && key_size != 8) return 0;
-	if (value_size != 0 && value_size != 4 && value_size != 8) return 0;
-	return (size_t) sbk_rows(key_size, value_size) * SBK_ROW_ELEMS;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size)) return 0;
+	return (size_t) clo_op_seg_rows(key_size, value_size) * SBK_ROW_ELEMS;
 }
 
-size_t clo_hip_scan_by_key_workspace_bytes(size_t numel) {
-	const size_t t = sbk_max_tiles(numel);
-	return sbk_align(t * sizeof(unsigned)) + sbk_align(t * sizeof(unsigned long long));
-}
+size_t clo_hip_scan_by_key_workspace_bytes(size_t numel) { return clo_op_seg_workspace_bytes(numel); }
 
 int clo_hip_scan_by_key(const void* keys_in, const void* values_in, void* out, size_t numel,
 	int key_size, int value_type, int sum_type, int op, int inclusive,
 	void* workspace, size_t workspace_bytes, void* stream) {
 	hipStream_t s = (hipStream_t) stream;
 	if (clo_ws_misaligned(workspace)) return CLO_HIP_EARGS;
-	if (op != SBK_SUM && op != SBK_MIN && op != SBK_MAX) return CLO_HIP_EARGS;
+	if (op != CLO_OP_SUM && op != CLO_OP_MIN && op != CLO_OP_MAX) return CLO_HIP_EARGS;
 	if (inclusive != 0 && inclusive != 1) return CLO_HIP_EARGS;
-	if (!values_in && op != SBK_SUM) return CLO_HIP_EARGS;   // the min / max of ones
+	if (!values_in && op != CLO_OP_SUM) return CLO_HIP_EARGS;   // the min / max of ones
 	if (numel > 0xffffffffull) return CLO_HIP_EARGS;
-	if (key_size != 1 && key_size != 2 && key_size != 4 && key_size != 8) return CLO_HIP_EUNSUPPORTED;
-	const int cvt = sbk_cvt_of(values_in != nullptr, value_type, sum_type);
+	if (!clo_op_key_size_ok(key_size)) return CLO_HIP_EUNSUPPORTED;
+	const int cvt = clo_op_cvt_of(true, values_in != nullptr, value_type, sum_type);
 	if (cvt < 0) return CLO_HIP_EUNSUPPORTED;
 	if (numel == 0) return 0;   // nothing to scan, no launch
 	if (!keys_in || !out || !workspace) return CLO_HIP_EARGS;
-	if (clo_misaligned(out, (size_t) sbk_type_size(sum_type))) return CLO_HIP_EARGS;
+	if (clo_misaligned(out, (size_t) clo_op_type_size(sum_type))) return CLO_HIP_EARGS;
 	if (workspace_bytes < clo_hip_scan_by_key_workspace_bytes(numel)) return CLO_HIP_EWORKSPACE;
 
 	sbk_args a;
 	a.keys_in = keys_in; a.values_in = values_in; a.out = out; a.n = numel; a.inclusive = inclusive; a.ws = workspace; a.s = s;
 	// min / max in a signed sum type: compared as unsigned numbers with the sign bit flipped
-	a.flip = (op != SBK_SUM && sbk_type_signed(sum_type)) ? 1ull << (8 * sbk_type_size(sum_type) - 1) : 0ull;
-	switch (key_size) {
-		case 1: return sbk_dispatch_cvt<uint8_t>(a, cvt, op);
-		case 2: return sbk_dispatch_cvt<uint16_t>(a, cvt, op);
-		case 4: return sbk_dispatch_cvt<uint32_t>(a, cvt, op);
-		default: return sbk_dispatch_cvt<uint64_t>(a, cvt, op);
-	}
+	a.flip = (op != CLO_OP_SUM && clo_op_type_signed(sum_type)) ? 1ull << (8 * clo_op_type_size(sum_type) - 1) : 0ull;
+	return clo_op_by_key_size(key_size, [&](auto tk) { return sbk_dispatch_cvt<decltype(tk)>(a, cvt, op); });
 }
 
 }  // extern "C"

@@ -17,15 +17,17 @@
 // positions written are <= numel_h and the trip counts depend on the sizes alone. A thread carries ITEMS needles
 // through the steps together, so that their loads are in flight at once.
 // Needles come in and positions go out through LDS: 16-byte vectors from the first 16-byte boundary on, single
-// elements before it and after the last whole vector, as in clo_hip_merge.hip.
+// elements before it and after the last whole vector (clo_op_stage, clo_hip_op_device.h).
 #include <hip/hip_runtime.h>
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
+#include "clo_hip_op_device.h"
 
 namespace {
 
 constexpr int SEARCH_THREADS = 256;
+static_assert(SEARCH_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS");
 constexpr int SEARCH_ITEMS = 4;
 constexpr unsigned SEARCH_TILE = SEARCH_THREADS * SEARCH_ITEMS;
 constexpr unsigned SEARCH_LDS_KEYS = 4096;
@@ -33,9 +35,6 @@ constexpr unsigned SEARCH_PIVOTS_LOG2 = 10;
 constexpr unsigned SEARCH_PIVOTS = 1u << SEARCH_PIVOTS_LOG2;
 constexpr unsigned SEARCH_GROUPS = 256 * 8;   // the general path's grid when the caller sets no bound
 static_assert(SEARCH_PIVOTS <= SEARCH_LDS_KEYS, "the pivots live where a staged haystack would");
-
-__device__ __forceinline__ unsigned search_min(unsigned a, unsigned b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned search_max(unsigned a, unsigned b) { return a > b ? a : b; }
 
 // For each of N needles x[k]: base[k] + how many keys of h[base[k], base[k] + n[k]) are < x[k] (upper: <= x[k]), the
 // keys ascending. nmax >= every n[k] sets the number of steps. Loads are of h[<= last] only; the callers pass a last
@@ -47,7 +46,7 @@ __device__ __forceinline__ void search_halve(const TK* h, unsigned (&base)[N], u
 	for (unsigned m = nmax; m > 1u; m -= m >> 1) {
 		TK v[N];
 		#pragma unroll
-		for (int k = 0; k < N; ++k) v[k] = h[search_min(base[k] + (n[k] >> 1) - (n[k] > 1u ? 1u : 0u), last)];
+		for (int k = 0; k < N; ++k) v[k] = h[clo_op_min(base[k] + (n[k] >> 1) - (n[k] > 1u ? 1u : 0u), last)];
 		#pragma unroll
 		for (int k = 0; k < N; ++k) {
 			const TK y = XF ? clo_keyx_fwd<TK>(v[k], kx) : v[k];
@@ -59,7 +58,7 @@ __device__ __forceinline__ void search_halve(const TK* h, unsigned (&base)[N], u
 	}
 	TK v[N];
 	#pragma unroll
-	for (int k = 0; k < N; ++k) v[k] = h[search_min(base[k], last)];
+	for (int k = 0; k < N; ++k) v[k] = h[clo_op_min(base[k], last)];
 	#pragma unroll
 	for (int k = 0; k < N; ++k) {
 		const TK y = XF ? clo_keyx_fwd<TK>(v[k], kx) : v[k];
@@ -77,30 +76,11 @@ __device__ __forceinline__ unsigned search_one(const TK* h, unsigned n, TK x, bo
 	return base[0];
 }
 
-// src[0, count) into dst[0, count) (LDS), lanes on adjacent 16-byte vectors from src's first 16-byte boundary on.
-template <typename T, bool XF>
-__device__ __forceinline__ void search_stage(const T* __restrict__ src, unsigned count, T* dst, const clo_keyx& kx, unsigned tid) {
-	constexpr unsigned PER = 16u / sizeof(T);
-	typedef T vec __attribute__((ext_vector_type(PER)));
-	const unsigned head = search_min((unsigned) ((16u - ((uintptr_t) src & 15u)) & 15u) / (unsigned) sizeof(T), count);
-	const unsigned nvec = (count - head) / PER, body_end = head + nvec * PER;
-	for (unsigned v = tid; v < nvec; v += SEARCH_THREADS) {
-		const unsigned i0 = head + v * PER;
-		const vec x = *reinterpret_cast<const vec*>(src + i0);
-		#pragma unroll
-		for (unsigned c = 0; c < PER; ++c) dst[i0 + c] = XF ? clo_keyx_fwd<T>(x[c], kx) : x[c];
-	}
-	const unsigned rest = head + (count - body_end);   // fewer than 2 PER <= 32 elements
-	if (tid < rest) {
-		const unsigned i = tid < head ? tid : body_end + (tid - head);
-		dst[i] = XF ? clo_keyx_fwd<T>(src[i], kx) : src[i];
-	}
-}
-
-// dst[0, count) = src[0, count) (LDS), the same division: 16-byte vector stores where dst allows them.
+// dst[0, count) = src[0, count) (LDS), clo_op_stage's division: 16-byte vector stores where dst allows them. (Not
+// clo_op_store: it copies from an array and calls no functor.)
 __device__ __forceinline__ void search_store(unsigned* __restrict__ dst, unsigned count, const unsigned* src, unsigned tid) {
 	typedef unsigned vec __attribute__((ext_vector_type(4)));
-	const unsigned head = search_min((unsigned) ((16u - ((uintptr_t) dst & 15u)) & 15u) / 4u, count);
+	const unsigned head = clo_op_min((unsigned) ((16u - ((uintptr_t) dst & 15u)) & 15u) / 4u, count);
 	const unsigned nvec = (count - head) / 4u, body_end = head + nvec * 4u;
 	for (unsigned v = tid; v < nvec; v += SEARCH_THREADS) {
 		const unsigned i0 = head + v * 4u;
@@ -135,7 +115,7 @@ void clo_search_kernel(const TK* __restrict__ hay, unsigned numel_h, const TK* _
 
 	if constexpr (!SORTED) {
 		if (whole) {
-			search_stage<TK, true>(hay, numel_h, s_hay, kx, tid);
+			clo_op_stage<TK, true>(hay, numel_h, s_hay, kx, tid);
 		} else {
 			for (unsigned k = tid; k < SEARCH_PIVOTS; k += SEARCH_THREADS)
 				s_hay[k] = clo_keyx_fwd<TK>(hay[search_pivot_at(k, numel_h)], kx);   // k numel_h / PIVOTS < numel_h
@@ -144,15 +124,15 @@ void clo_search_kernel(const TK* __restrict__ hay, unsigned numel_h, const TK* _
 
 	for (unsigned tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
 		const unsigned n0 = tile * SEARCH_TILE;                         // tiles * TILE < 2^32 + TILE: n0 < numel_n does not wrap
-		const unsigned cnt = search_min(SEARCH_TILE, numel_n - n0);     // the clamp of the last partial tile
-		search_stage<TK, true>(ndl + n0, cnt, s_ndl, kx, tid);
+		const unsigned cnt = clo_op_min(SEARCH_TILE, numel_n - n0);     // the clamp of the last partial tile
+		clo_op_stage<TK, true>(ndl + n0, cnt, s_ndl, kx, tid);
 
 		// the tile's range [r0, r0 + len) of the haystack: the partition's two results clamped to r0 <= r1 <= numel_h
 		unsigned r0 = 0u, len = numel_h;
 		if constexpr (SORTED) {
-			r0 = search_min(part[2u * tile], numel_h);
-			len = search_min(search_max(part[2u * tile + 1u], r0), numel_h) - r0;
-			if (len > 0u && len <= SEARCH_LDS_KEYS) search_stage<TK, true>(hay + r0, len, s_hay, kx, tid);
+			r0 = clo_op_min(part[2u * tile], numel_h);
+			len = clo_op_min(clo_op_max(part[2u * tile + 1u], r0), numel_h) - r0;
+			if (len > 0u && len <= SEARCH_LDS_KEYS) clo_op_stage<TK, true>(hay + r0, len, s_hay, kx, tid);
 		}
 		__syncthreads();   // s_ndl, s_hay; and every thread has left the previous tile's store of s_pos
 
@@ -199,7 +179,7 @@ void clo_search_partition_kernel(const TK* __restrict__ hay, unsigned numel_h, c
 	clo_keyx kx, unsigned* __restrict__ part) {
 	const unsigned t = blockIdx.x * SEARCH_THREADS + threadIdx.x;
 	if (t >= tiles) return;
-	const unsigned n0 = t * SEARCH_TILE, n1 = n0 + search_min(SEARCH_TILE, numel_n - n0);   // n0 < n1 <= numel_n
+	const unsigned n0 = t * SEARCH_TILE, n1 = n0 + clo_op_min(SEARCH_TILE, numel_n - n0);   // n0 < n1 <= numel_n
 	part[2u * t] = search_one<TK>(hay, numel_h, clo_keyx_fwd<TK>(ndl[n0], kx), false, kx);
 	part[2u * t + 1u] = search_one<TK>(hay, numel_h, clo_keyx_fwd<TK>(ndl[n1 - 1u], kx), true, kx);
 }
@@ -233,7 +213,6 @@ int search_launch(const search_args& a) {
 	return (int) hipGetLastError();
 }
 
-inline bool search_key_size_ok(int ks) { return ks == 1 || ks == 2 || ks == 4 || ks == 8; }
 // the partition is worth its launch only where there is a haystack to partition
 inline bool search_partitions(size_t numel_h, size_t numel_n, unsigned flags) {
 	return (flags & CLO_HIP_SEARCH_NEEDLES_SORTED) != 0 && numel_h > 0 && numel_n > 0;
@@ -243,21 +222,20 @@ inline bool search_partitions(size_t numel_h, size_t numel_n, unsigned flags) {
 
 extern "C" {
 
-size_t clo_hip_search_tile(int key_size) { return search_key_size_ok(key_size) ? SEARCH_TILE : 0; }
-size_t clo_hip_search_lds_keys(int key_size) { return search_key_size_ok(key_size) ? SEARCH_LDS_KEYS : 0; }
-size_t clo_hip_search_pivots(int key_size) { return search_key_size_ok(key_size) ? SEARCH_PIVOTS : 0; }
+size_t clo_hip_search_tile(int key_size) { return clo_op_key_size_ok(key_size) ? SEARCH_TILE : 0; }
+size_t clo_hip_search_lds_keys(int key_size) { return clo_op_key_size_ok(key_size) ? SEARCH_LDS_KEYS : 0; }
+size_t clo_hip_search_pivots(int key_size) { return clo_op_key_size_ok(key_size) ? SEARCH_PIVOTS : 0; }
 
 size_t clo_hip_search_workspace_bytes(size_t numel_h, size_t numel_n, unsigned flags) {
 	if (!search_partitions(numel_h, numel_n, flags)) return 0;
 	// two words per tile, in whole CLO_HIP_WORKSPACE_ALIGN units
-	const size_t bytes = ((numel_n + SEARCH_TILE - 1) / SEARCH_TILE) * 2 * sizeof(unsigned);
-	return (bytes + CLO_HIP_WORKSPACE_ALIGN - 1) / CLO_HIP_WORKSPACE_ALIGN * CLO_HIP_WORKSPACE_ALIGN;
+	return clo_op_ws_align(((numel_n + SEARCH_TILE - 1) / SEARCH_TILE) * 2 * sizeof(unsigned));
 }
 
 int clo_hip_search(const void* haystack, size_t numel_h, const void* needles, size_t numel_n, void* pos_out,
 	int key_size, int key_kind, unsigned flags, unsigned max_groups, void* workspace, size_t workspace_bytes, void* stream) {
 	if (key_kind < 0 || key_kind > 2) return CLO_HIP_EARGS;
-	if (!search_key_size_ok(key_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
+	if (!clo_op_key_size_ok(key_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
 	if (flags & ~(CLO_HIP_SEARCH_UPPER | CLO_HIP_SEARCH_NEEDLES_SORTED)) return CLO_HIP_EARGS;
 	if (numel_h > 0xffffffffull || numel_n > 0xffffffffull) return CLO_HIP_EARGS;
 	if (numel_h > 0 && !haystack) return CLO_HIP_EARGS;
@@ -278,12 +256,7 @@ int clo_hip_search(const void* haystack, size_t numel_h, const void* needles, si
 	a.sorted = need > 0;
 	a.kx = clo_keyx_make(key_kind, 0, 8 * key_size);
 	a.part = (unsigned*) workspace; a.s = (hipStream_t) stream;
-	switch (key_size) {
-		case 1: return search_launch<uint8_t>(a);
-		case 2: return search_launch<uint16_t>(a);
-		case 4: return search_launch<uint32_t>(a);
-		default: return search_launch<uint64_t>(a);
-	}
+	return clo_op_by_key_size(key_size, [&](auto tk) { return search_launch<decltype(tk)>(a); });
 }
 
 }  // extern "C"

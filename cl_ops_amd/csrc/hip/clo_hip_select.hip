@@ -23,6 +23,7 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
+#include "clo_hip_op_device.h"
 
 namespace {
 
@@ -30,6 +31,7 @@ constexpr int SEL_THREADS = 256;
 constexpr int SEL_WAVES = SEL_THREADS / 64;
 constexpr int SEL_VEC = 4;
 constexpr int SEL_ROW_ELEMS = SEL_THREADS * SEL_VEC;   // 1024
+static_assert(SEL_THREADS == CLO_OP_THREADS && SEL_VEC == CLO_OP_VEC, "the shared helpers' work-group and vector");
 constexpr int SEL_CHUNK_ROWS = 4;                      // the count sweep takes the rows of a tile four at a time
 constexpr unsigned SEL_SCAN_ITEMS = 8;                 // the scan sweeps SEL_THREADS * SEL_SCAN_ITEMS counts per trip
 static_assert(SEL_THREADS * SEL_SCAN_ITEMS == CLO_HIP_SELECT_SCAN_TRIP, "the header names the scan's trip");
@@ -38,35 +40,9 @@ static_assert(SEL_THREADS * SEL_SCAN_ITEMS == CLO_HIP_SELECT_SCAN_TRIP, "the hea
 constexpr int sel_rows(int key_size, int value_size) { return (key_size > value_size ? key_size : value_size) <= 4 ? 8 : 4; }
 constexpr size_t sel_tile(int key_size, int value_size) { return (size_t) sel_rows(key_size, value_size) * SEL_ROW_ELEMS; }
 
-enum { SEL_KEYS = 0, SEL_V4 = 1, SEL_V8 = 2, SEL_ARG = 3 };
-template <int MODE> struct sel_val { typedef uint32_t T; static constexpr int size = MODE == SEL_KEYS ? 0 : 4; };
-template <> struct sel_val<SEL_V8> { typedef unsigned long long T; static constexpr int size = 8; };
-
-__device__ __forceinline__ unsigned sel_min(unsigned a, unsigned b) { return a < b ? a : b; }
-
-// Four consecutive elements from element index i0 (a multiple of 4) of an array of n: 16-byte (or 4 elements') vector
-// loads where the array's start allows them (vec_ok) and all four exist, else one by one; elements past the end read
-// as 0.
-template <typename T>
-__device__ __forceinline__ void sel_load4(const T* __restrict__ p, size_t i0, size_t n, bool vec_ok, T (&v)[SEL_VEC]) {
-	if (vec_ok && i0 + SEL_VEC <= n) {
-		if constexpr (sizeof(T) == 8) {
-			typedef T vec2 __attribute__((ext_vector_type(2)));
-			const vec2 a = *reinterpret_cast<const vec2*>(p + i0), b = *reinterpret_cast<const vec2*>(p + i0 + 2);
-			v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-		} else {
-			typedef T vec4 __attribute__((ext_vector_type(4)));
-			const vec4 x = *reinterpret_cast<const vec4*>(p + i0);
-			v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-		}
-	} else {
-		#pragma unroll
-		for (int c = 0; c < SEL_VEC; ++c) v[c] = i0 + c < n ? p[i0 + c] : (T) 0;
-	}
-}
-// what vec_ok asks of the array's start
-template <typename T>
-inline int sel_vec_ok(const void* p) { return !clo_misaligned(p, sizeof(T) * SEL_VEC < 16 ? sizeof(T) * SEL_VEC : 16); }
+// the modes CLO_OP_KEYS, V4, V8 and ARG (clo_hip_op_device.h); the table keeps a name of its own here because the
+// kernels' symbols spell it
+template <int MODE> struct sel_val : clo_op_val<MODE> {};
 
 // The order-key function of merge and search (clo_keyx_fwd), its kind known when the kernel is compiled.
 template <typename TK, int KIND>
@@ -98,11 +74,11 @@ __device__ __forceinline__ unsigned sel_decide(const sel_pred<TK>& q, size_t i0,
 	unsigned bits = 0;
 	if constexpr (FLAGGED) {
 		unsigned char f[SEL_VEC];
-		sel_load4<unsigned char>(q.flags, i0, q.n, q.fvec, f);
+		clo_op_load4<unsigned char>(q.flags, i0, q.n, q.fvec, f);
 		#pragma unroll
 		for (int c = 0; c < SEL_VEC; ++c) bits |= (f[c] != 0 ? 1u : 0u) << c;   // past the end: read as 0
 	} else {
-		sel_load4<TK>(q.keys, i0, q.n, q.kvec, k);
+		clo_op_load4<TK>(q.keys, i0, q.n, q.kvec, k);
 		// which of below / equal / above the threshold the predicate keeps (wave-uniform)
 		const bool below = q.pred == CLO_HIP_SELECT_LT || q.pred == CLO_HIP_SELECT_LE || q.pred == CLO_HIP_SELECT_NE;
 		const bool equal = q.pred == CLO_HIP_SELECT_LE || q.pred == CLO_HIP_SELECT_GE || q.pred == CLO_HIP_SELECT_EQ;
@@ -201,28 +177,6 @@ void clo_select_scan_kernel(unsigned* __restrict__ count, unsigned tiles, unsign
 	}
 }
 
-// dst[i] = get(i) for i in [0, count): lanes on adjacent 16-byte vectors from dst's first 16-byte boundary on, the
-// fewer than two vectors' worth before and after it element by element.
-template <typename T, typename F>
-__device__ __forceinline__ void sel_store(T* __restrict__ dst, unsigned count, unsigned tid, F get) {
-	constexpr unsigned PER = 16u / sizeof(T);
-	typedef T vec __attribute__((ext_vector_type(PER)));
-	const unsigned head = sel_min((unsigned) ((16u - ((uintptr_t) dst & 15u)) & 15u) / (unsigned) sizeof(T), count);
-	const unsigned nvec = (count - head) / PER, body_end = head + nvec * PER;
-	for (unsigned v = tid; v < nvec; v += SEL_THREADS) {
-		const unsigned i0 = head + v * PER;
-		vec x;
-		#pragma unroll
-		for (unsigned c = 0; c < PER; ++c) x[c] = get(i0 + c);
-		*reinterpret_cast<vec*>(dst + i0) = x;
-	}
-	const unsigned rest = head + (count - body_end);   // fewer than 2 PER <= 32 elements
-	if (tid < rest) {
-		const unsigned i = tid < head ? tid : body_end + (tid - head);
-		dst[i] = get(i);
-	}
-}
-
 // Where the tile's rows go. The kept rows of tile t start at row offset[t]; the rejected ones of a partition at k + (the
 // rejected rows before the tile) = k + (tile start - offset[t]). Both are clamped to [0, numel).
 struct sel_place { unsigned keep_at, keep_rows, rej_at, rej_rows; };
@@ -237,8 +191,8 @@ void clo_select_apply_kernel(const TK* __restrict__ keys, const typename sel_val
 	constexpr int ROWS = sel_rows((int) sizeof(TK), sel_val<MODE>::size);
 	constexpr unsigned TILE = (unsigned) ROWS * SEL_ROW_ELEMS;
 	constexpr int PIECES = ROWS * SEL_WAVES;
-	constexpr bool VALS = MODE == SEL_V4 || MODE == SEL_V8;
-	constexpr size_t ELEM = MODE != SEL_KEYS && sizeof(TV) > sizeof(TK) ? sizeof(TV) : sizeof(TK);
+	constexpr bool VALS = MODE == CLO_OP_V4 || MODE == CLO_OP_V8;
+	constexpr size_t ELEM = MODE != CLO_OP_KEYS && sizeof(TV) > sizeof(TK) ? sizeof(TV) : sizeof(TK);
 	static_assert(PIECES <= 64, "one piece per lane");
 	__shared__ __attribute__((aligned(16))) unsigned char s_buf[TILE * ELEM];
 	__shared__ unsigned s_piece[PIECES];
@@ -258,15 +212,15 @@ void clo_select_apply_kernel(const TK* __restrict__ keys, const typename sel_val
 		for (int r = 0; r < ROWS; ++r) {
 			const size_t i0 = base + (size_t) r * SEL_ROW_ELEMS;
 			bits[r] = sel_decide<TK, KIND, true>(q, i0, k[r]);
-			sel_load4<TK>(keys, i0, n_keys, kvec != 0, k[r]);
-			if constexpr (VALS) sel_load4<TV>(values, i0, n, vvec != 0, v[r]);
+			clo_op_load4<TK>(keys, i0, n_keys, kvec != 0, k[r]);
+			if constexpr (VALS) clo_op_load4<TV>(values, i0, n, vvec != 0, v[r]);
 		}
 	} else {
 		#pragma unroll
 		for (int r = 0; r < ROWS; ++r) {
 			const size_t i0 = base + (size_t) r * SEL_ROW_ELEMS;
 			bits[r] = sel_decide<TK, KIND, false>(q, i0, k[r]);
-			if constexpr (VALS) sel_load4<TV>(values, i0, n, vvec != 0, v[r]);
+			if constexpr (VALS) clo_op_load4<TV>(values, i0, n, vvec != 0, v[r]);
 		}
 	}
 	// a lane's rank inside its wave's row; the wave totals are the tile's pieces
@@ -314,15 +268,15 @@ void clo_select_apply_kernel(const TK* __restrict__ keys, const typename sel_val
 			}
 		}
 		__syncthreads();
-		sel_store(out + pl.keep_at, pl.keep_rows, tid, [&](unsigned j) { return s[j]; });
-		if (partition) sel_store(out + pl.rej_at, pl.rej_rows, tid, [&](unsigned j) { return s[kept + j]; });
+		clo_op_store(out + pl.keep_at, pl.keep_rows, tid, [&](unsigned j) { return s[j]; });
+		if (partition) clo_op_store(out + pl.rej_at, pl.rej_rows, tid, [&](unsigned j) { return s[kept + j]; });
 	};
 	if (want_keys) {
 		compact(reinterpret_cast<TK*>(s_buf), kout, [&](int r, int c, unsigned) { return k[r][c]; });
-		if constexpr (MODE != SEL_KEYS) __syncthreads();   // the values take the keys' place
+		if constexpr (MODE != CLO_OP_KEYS) __syncthreads();   // the values take the keys' place
 	}
 	if constexpr (VALS) compact(reinterpret_cast<TV*>(s_buf), vout, [&](int r, int c, unsigned) { return v[r][c]; });
-	if constexpr (MODE == SEL_ARG) compact(reinterpret_cast<TV*>(s_buf), vout, [&](int, int, unsigned idx) { return (TV) (tile_start + idx); });
+	if constexpr (MODE == CLO_OP_ARG) compact(reinterpret_cast<TV*>(s_buf), vout, [&](int, int, unsigned idx) { return (TV) (tile_start + idx); });
 }
 
 struct sel_args {
@@ -342,8 +296,8 @@ int sel_launch(const sel_args& a) {
 	constexpr int ROWS = sel_rows((int) sizeof(TK), sel_val<MODE>::size);
 	constexpr size_t TILE = (size_t) ROWS * SEL_ROW_ELEMS;
 	const unsigned tiles = (unsigned) ((a.n + TILE - 1) / TILE);
-	const int kvec = sel_vec_ok<TK>(a.keys), vvec = sel_vec_ok<TV>(a.values);
-	const int fvec = a.pred == CLO_HIP_SELECT_FLAGGED ? sel_vec_ok<unsigned char>(a.fot) : 0;
+	const int kvec = clo_op_vec_ok<TK>(a.keys), vvec = clo_op_vec_ok<TV>(a.values);
+	const int fvec = a.pred == CLO_HIP_SELECT_FLAGGED ? clo_op_vec_ok<unsigned char>(a.fot) : 0;
 	unsigned* count = a.ws;   // tiles + 1 words: the counts, then the offsets and the total
 	{
 		clo_timing_scope timing("select_count", a.s);
@@ -364,10 +318,10 @@ int sel_launch(const sel_args& a) {
 template <typename TK, int KIND>
 int sel_dispatch_mode(const sel_args& a, int mode) {
 	switch (mode) {
-		case SEL_KEYS: return sel_launch<TK, KIND, SEL_KEYS>(a);
-		case SEL_V4: return sel_launch<TK, KIND, SEL_V4>(a);
-		case SEL_V8: return sel_launch<TK, KIND, SEL_V8>(a);
-		default: return sel_launch<TK, KIND, SEL_ARG>(a);
+		case CLO_OP_KEYS: return sel_launch<TK, KIND, CLO_OP_KEYS>(a);
+		case CLO_OP_V4: return sel_launch<TK, KIND, CLO_OP_V4>(a);
+		case CLO_OP_V8: return sel_launch<TK, KIND, CLO_OP_V8>(a);
+		default: return sel_launch<TK, KIND, CLO_OP_ARG>(a);
 	}
 }
 
@@ -380,15 +334,12 @@ int sel_dispatch(const sel_args& a, int kind, int mode) {
 	return sel_dispatch_mode<TK, 0>(a, mode);
 }
 
-inline bool sel_key_size_ok(int ks) { return ks == 1 || ks == 2 || ks == 4 || ks == 8; }
-inline bool sel_value_size_ok(int vs) { return vs == 0 || vs == 4 || vs == 8; }
-
 }  // namespace
 
 extern "C" {
 
 size_t clo_hip_select_tile(int key_size, int value_size) {
-	if (!sel_key_size_ok(key_size) || !sel_value_size_ok(value_size)) return 0;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size)) return 0;
 	return sel_tile(key_size, value_size);
 }
 
@@ -396,8 +347,7 @@ size_t clo_hip_select_workspace_bytes(size_t numel, int key_size, int value_size
 	const size_t tile = clo_hip_select_tile(key_size, value_size);
 	if (numel == 0 || tile == 0) return 0;
 	// one count per tile and the total, 4 bytes each, in whole CLO_HIP_WORKSPACE_ALIGN units
-	const size_t bytes = ((numel - 1) / tile + 2) * sizeof(unsigned);
-	return (bytes + CLO_HIP_WORKSPACE_ALIGN - 1) / CLO_HIP_WORKSPACE_ALIGN * CLO_HIP_WORKSPACE_ALIGN;
+	return clo_op_ws_align(((numel - 1) / tile + 2) * sizeof(unsigned));
 }
 
 int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in, const void* flags_or_threshold,
@@ -406,7 +356,7 @@ int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in,
 	if (op != CLO_HIP_SELECT_SELECT && op != CLO_HIP_SELECT_PARTITION) return CLO_HIP_EARGS;
 	if (pred < CLO_HIP_SELECT_FLAGGED || pred > CLO_HIP_SELECT_NE) return CLO_HIP_EARGS;
 	if (key_kind < 0 || key_kind > 2) return CLO_HIP_EARGS;
-	if (!sel_key_size_ok(key_size) || !sel_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
 	if (numel > 0xffffffffull) return CLO_HIP_EARGS;
 	if (!flags_or_threshold && (numel > 0 || pred != CLO_HIP_SELECT_FLAGGED)) return CLO_HIP_EARGS;
 	if (!num_out || clo_misaligned(num_out, 8)) return CLO_HIP_EARGS;
@@ -430,13 +380,8 @@ int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in,
 	a.keys = keys_in; a.values = values_in; a.fot = flags_or_threshold; a.kout = keys_out; a.vout = values_out;
 	a.n = numel; a.pred = pred; a.op = op;
 	a.ws = (unsigned*) workspace; a.num_out = (unsigned long long*) num_out; a.s = (hipStream_t) stream;
-	const int mode = value_size == 0 ? SEL_KEYS : arg ? SEL_ARG : value_size == 4 ? SEL_V4 : SEL_V8;
-	switch (key_size) {
-		case 1: return sel_dispatch<uint8_t>(a, key_kind, mode);
-		case 2: return sel_dispatch<uint16_t>(a, key_kind, mode);
-		case 4: return sel_dispatch<uint32_t>(a, key_kind, mode);
-		default: return sel_dispatch<uint64_t>(a, key_kind, mode);
-	}
+	const int mode = clo_op_mode(value_size, arg);
+	return clo_op_by_key_size(key_size, [&](auto tk) { return sel_dispatch<decltype(tk)>(a, key_kind, mode); });
 }
 
 }  // extern "C"

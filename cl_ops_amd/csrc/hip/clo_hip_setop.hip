@@ -28,22 +28,21 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
+#include "clo_hip_op_device.h"
 
 namespace {
 
 constexpr int SETOP_THREADS = 256;
+static_assert(SETOP_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS");
 constexpr int SETOP_WAVES = SETOP_THREADS / 64;
 constexpr int setop_items(int key_size) { return key_size <= 2 ? 17 : 9; }
 constexpr size_t setop_tile(int key_size) { return (size_t) SETOP_THREADS * setop_items(key_size); }
 constexpr size_t SETOP_MIN_TILE = setop_tile(8);   // sizes the workspace, whose getter does not know the key size
 constexpr unsigned SETOP_SCAN_ITEMS = 8;           // the scan sweeps SETOP_THREADS * SETOP_SCAN_ITEMS counts at a time
 
-enum { SETOP_KEYS = 0, SETOP_V4 = 1, SETOP_V8 = 2, SETOP_ARG = 3 };
-template <int MODE> struct setop_val { typedef uint32_t T; };
-template <> struct setop_val<SETOP_V8> { typedef unsigned long long T; };
-
-__device__ __forceinline__ unsigned setop_min(unsigned a, unsigned b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned setop_max(unsigned a, unsigned b) { return a > b ? a : b; }
+// the modes CLO_OP_KEYS, V4, V8 and ARG (clo_hip_op_device.h); the table keeps a name of its own here because the
+// kernels' symbols spell it
+template <int MODE> struct setop_val : clo_op_val<MODE> {};
 
 // The keep rule. matched: the element has a partner of the same rank in the other array's run of its key.
 __device__ __forceinline__ bool setop_keep(int op, bool from_a, bool matched) {
@@ -53,20 +52,6 @@ __device__ __forceinline__ bool setop_keep(int op, bool from_a, bool matched) {
 		case CLO_HIP_SETOP_DIFFERENCE: return from_a && !matched;
 		default: return !matched;
 	}
-}
-
-// The merge's diagonal search (clo_hip_merge.hip): how many of the first d outputs of merging a[0, na) and b[0, nb)
-// come from a, ties going to a. The result lies in [max(0, d - nb), min(d, na)]; only a[< na] and b[< nb] are read.
-template <typename TK, bool XF>
-__device__ __forceinline__ unsigned setop_path(const TK* a, const TK* b, unsigned na, unsigned nb, unsigned d, const clo_keyx& kx) {
-	unsigned lo = d > nb ? d - nb : 0u, hi = setop_min(d, na);
-	while (lo < hi) {
-		const unsigned mid = lo + ((hi - lo) >> 1);
-		TK x = a[mid], y = b[d - 1u - mid];
-		if constexpr (XF) { x = clo_keyx_fwd<TK>(x, kx); y = clo_keyx_fwd<TK>(y, kx); }
-		if (x <= y) lo = mid + 1u; else hi = mid;
-	}
-	return lo;
 }
 
 // The first index in [lo, hi) whose key is not below x (UPPER: is above x), hi if there is none. Reads k[lo, hi) only.
@@ -85,55 +70,12 @@ template <typename TK>
 __global__ __launch_bounds__(SETOP_THREADS)
 void clo_setop_partition_kernel(const TK* __restrict__ ka, const TK* __restrict__ kb, unsigned na, unsigned nb, unsigned tiles,
 	clo_keyx kx, unsigned* __restrict__ split) {
-	const unsigned t = blockIdx.x * SETOP_THREADS + threadIdx.x;
-	if (t > tiles) return;
-	const unsigned long long n = (unsigned long long) na + nb, dd = (unsigned long long) t * setop_tile((int) sizeof(TK));
-	split[t] = setop_path<TK, true>(ka, kb, na, nb, (unsigned) (dd < n ? dd : n), kx);
-}
-
-// src[0, count) into dst[0, count) (LDS), lanes on adjacent 16-byte vectors from src's first 16-byte boundary on.
-template <typename T, bool XF>
-__device__ __forceinline__ void setop_stage(const T* __restrict__ src, unsigned count, T* dst, const clo_keyx& kx, unsigned tid) {
-	constexpr unsigned PER = 16u / sizeof(T);
-	typedef T vec __attribute__((ext_vector_type(PER)));
-	const unsigned head = setop_min((unsigned) ((16u - ((uintptr_t) src & 15u)) & 15u) / (unsigned) sizeof(T), count);
-	const unsigned nvec = (count - head) / PER, body_end = head + nvec * PER;
-	for (unsigned v = tid; v < nvec; v += SETOP_THREADS) {
-		const unsigned i0 = head + v * PER;
-		const vec x = *reinterpret_cast<const vec*>(src + i0);
-		#pragma unroll
-		for (unsigned c = 0; c < PER; ++c) dst[i0 + c] = XF ? clo_keyx_fwd<T>(x[c], kx) : x[c];
-	}
-	const unsigned rest = head + (count - body_end);   // fewer than 2 PER <= 32 elements
-	if (tid < rest) {
-		const unsigned i = tid < head ? tid : body_end + (tid - head);
-		dst[i] = XF ? clo_keyx_fwd<T>(src[i], kx) : src[i];
-	}
-}
-
-// dst[i] = get(i) for i in [0, count), the same division: 16-byte vector stores where dst allows them.
-template <typename T, typename F>
-__device__ __forceinline__ void setop_store(T* __restrict__ dst, unsigned count, unsigned tid, F get) {
-	constexpr unsigned PER = 16u / sizeof(T);
-	typedef T vec __attribute__((ext_vector_type(PER)));
-	const unsigned head = setop_min((unsigned) ((16u - ((uintptr_t) dst & 15u)) & 15u) / (unsigned) sizeof(T), count);
-	const unsigned nvec = (count - head) / PER, body_end = head + nvec * PER;
-	for (unsigned v = tid; v < nvec; v += SETOP_THREADS) {
-		const unsigned i0 = head + v * PER;
-		vec x;
-		#pragma unroll
-		for (unsigned c = 0; c < PER; ++c) x[c] = get(i0 + c);
-		*reinterpret_cast<vec*>(dst + i0) = x;
-	}
-	const unsigned rest = head + (count - body_end);
-	if (tid < rest) {
-		const unsigned i = tid < head ? tid : body_end + (tid - head);
-		dst[i] = get(i);
-	}
+	clo_op_partition<TK, setop_tile((int) sizeof(TK))>(ka, kb, na, nb, tiles, kx, split);
 }
 
 // The exclusive sum of v over the work-group's threads and the sum of all. One barrier; s_wave must not be written
-// again before every thread has left.
+// again before every thread has left. (Not clo_op_block_scan: the waves are scanned with __shfl_up here, which is
+// another sequence of instructions.)
 __device__ __forceinline__ unsigned setop_block_scan(unsigned v, unsigned* s_wave, unsigned tid, unsigned& total) {
 	const unsigned lane = tid & 63u;
 	unsigned inc = v;
@@ -155,33 +97,11 @@ __device__ __forceinline__ unsigned setop_block_scan(unsigned v, unsigned* s_wav
 	return before + inc - v;
 }
 
-// The tile's outputs [d0, d0 + cnt) of the MERGE and its ranges [a0, a0 + na_t) of A and [b0, b0 + nb_t) of B. The
-// searches' results are clamped to what d0, d1, na and nb alone allow, as in clo_merge_kernel: a0 in [d0 - nb, min(d0,
-// na)], a1 - a0 in [0, d1 - d0], a1 in [d1 - nb, na]. (Sorted inputs: nothing is changed.)
-struct setop_range { unsigned d0, cnt, a0, b0, na_t, nb_t; };
-
-template <unsigned TILE>
-__device__ __forceinline__ setop_range setop_tile_range(const unsigned* __restrict__ split, unsigned na, unsigned nb) {
-	const unsigned long long n = (unsigned long long) na + nb, dd0 = (unsigned long long) blockIdx.x * TILE;
-	const unsigned d0 = (unsigned) (dd0 < n ? dd0 : n), d1 = (unsigned) (dd0 + TILE < n ? dd0 + TILE : n);
-	setop_range r;
-	r.d0 = d0;
-	r.cnt = d1 - d0;
-	unsigned a0 = split[blockIdx.x], a1 = split[blockIdx.x + 1u];
-	a0 = setop_min(setop_max(a0, d0 > nb ? d0 - nb : 0u), setop_min(d0, na));
-	a1 = setop_min(setop_max(a1, setop_max(a0, d1 > nb ? d1 - nb : 0u)), setop_min(na, a0 + r.cnt));
-	r.a0 = a0;
-	r.b0 = d0 - a0;
-	r.na_t = a1 - a0;
-	r.nb_t = r.cnt - r.na_t;
-	return r;
-}
-
 // Lane 0 of wave w loads the key next to the tile that decides whether a run reaches outside it: w = 0 A[a0 - 1], 1 B[b0 -
 // 1], 2 A[a1], 3 B[b1] (unsigned order; ok: there is one). Requested before the tile is staged, looked at after it.
 template <typename TK>
 __device__ __forceinline__ TK setop_neighbour(const TK* __restrict__ ka, const TK* __restrict__ kb, unsigned na, unsigned nb,
-	const setop_range& r, const clo_keyx& kx, unsigned tid, bool& ok) {
+	const clo_op_range& r, const clo_keyx& kx, unsigned tid, bool& ok) {
 	ok = false;
 	if ((tid & 63u) != 0) return (TK) 0;
 	const unsigned w = tid >> 6, a1 = r.a0 + r.na_t, b1 = r.b0 + r.nb_t;
@@ -196,14 +116,14 @@ __device__ __forceinline__ TK setop_neighbour(const TK* __restrict__ ka, const T
 // slot[i] the LDS slot of output tid * ITEMS + i. One barrier inside. s_g: four words of LDS.
 template <typename TK, int ITEMS>
 __device__ __forceinline__ unsigned setop_decide(const TK* __restrict__ ka, const TK* __restrict__ kb, unsigned na, unsigned nb,
-	const setop_range& r, const TK* s_keys, unsigned* s_g, TK nbr, bool nbr_ok, int op, const clo_keyx& kx, unsigned tid,
+	const clo_op_range& r, const TK* s_keys, unsigned* s_g, TK nbr, bool nbr_ok, int op, const clo_keyx& kx, unsigned tid,
 	TK (&out)[ITEMS], unsigned (&slot)[ITEMS]) {
 	constexpr unsigned TILE = (unsigned) SETOP_THREADS * ITEMS;
 	const unsigned na_t = r.na_t, nb_t = r.nb_t, cnt = r.cnt, a0 = r.a0, b0 = r.b0;
 	const TK* sa = s_keys;
 	const TK* sb = s_keys + na_t;
 	// the tile's first and last key (cnt > 0): only their runs can begin before the tile or end after it
-	const TK a_lo = s_keys[0], a_hi = s_keys[na_t > 0 ? na_t - 1u : 0u], b_lo = s_keys[setop_min(na_t, TILE - 1u)], b_hi = s_keys[cnt - 1u];
+	const TK a_lo = s_keys[0], a_hi = s_keys[na_t > 0 ? na_t - 1u : 0u], b_lo = s_keys[clo_op_min(na_t, TILE - 1u)], b_hi = s_keys[cnt - 1u];
 	const TK kfirst = na_t == 0 ? b_lo : nb_t == 0 ? a_lo : (a_lo < b_lo ? a_lo : b_lo);
 	const TK klast = na_t == 0 ? b_hi : nb_t == 0 ? a_hi : (a_hi > b_hi ? a_hi : b_hi);
 	if ((tid & 63u) == 0) {
@@ -216,13 +136,13 @@ __device__ __forceinline__ unsigned setop_decide(const TK* __restrict__ ka, cons
 		s_g[w] = g;
 	}
 	// this thread's ITEMS outputs start at diagonal tid * ITEMS of the tile; past cnt nothing is valid
-	const unsigned diag = setop_min(tid * ITEMS, cnt);
-	unsigned ai = setop_path<TK, false>(sa, sb, na_t, nb_t, diag, kx);
+	const unsigned diag = clo_op_min(tid * ITEMS, cnt);
+	unsigned ai = clo_op_path<TK, false>(sa, sb, na_t, nb_t, diag, kx);
 	unsigned bi = diag - ai;
 	__syncthreads();
 	const unsigned g_lba = s_g[0], g_lbb = s_g[1], g_uba = s_g[2], g_ubb = s_g[3];
 
-	TK x = s_keys[setop_min(ai, TILE - 1u)], y = s_keys[setop_min(na_t + bi, TILE - 1u)];
+	TK x = s_keys[clo_op_min(ai, TILE - 1u)], y = s_keys[clo_op_min(na_t + bi, TILE - 1u)];
 	// the keys just before them, pa = A[ai - 1] and pb = B[bi - 1] where there are such: carried along in registers
 	bool has_pa = ai > 0, has_pb = bi > 0;
 	TK pa = s_keys[has_pa ? ai - 1u : 0u], pb = s_keys[has_pb ? na_t + bi - 1u : 0u];
@@ -263,7 +183,7 @@ __device__ __forceinline__ unsigned setop_decide(const TK* __restrict__ ka, cons
 			if (setop_keep(op, from_a, matched)) keep |= 1u << i;
 		}
 		if (from_a) { pa = x; has_pa = true; ++ai; } else { pb = y; has_pb = true; ++bi; }
-		const TK next = s_keys[setop_min(from_a ? ai : na_t + bi, TILE - 1u)];
+		const TK next = s_keys[clo_op_min(from_a ? ai : na_t + bi, TILE - 1u)];
 		if (from_a) x = next; else y = next;
 	}
 	return keep;
@@ -278,11 +198,11 @@ void clo_setop_count_kernel(const TK* __restrict__ ka, unsigned na, const TK* __
 	__shared__ __attribute__((aligned(16))) TK s_keys[TILE];
 	__shared__ unsigned s_g[4], s_wave[SETOP_WAVES];
 	const unsigned tid = threadIdx.x;
-	const setop_range r = setop_tile_range<TILE>(split, na, nb);
+	const clo_op_range r = clo_op_tile_range<TILE>(split, na, nb);
 	bool nbr_ok;
 	const TK nbr = setop_neighbour<TK>(ka, kb, na, nb, r, kx, tid, nbr_ok);
-	setop_stage<TK, true>(ka + r.a0, r.na_t, s_keys, kx, tid);
-	setop_stage<TK, true>(kb + r.b0, r.nb_t, s_keys + r.na_t, kx, tid);
+	clo_op_stage<TK, true>(ka + r.a0, r.na_t, s_keys, kx, tid);
+	clo_op_stage<TK, true>(kb + r.b0, r.nb_t, s_keys + r.na_t, kx, tid);
 	__syncthreads();
 	TK out[ITEMS];
 	unsigned slot[ITEMS];
@@ -338,23 +258,23 @@ void clo_setop_apply_kernel(const TK* __restrict__ ka, const typename setop_val<
 	typedef typename setop_val<MODE>::T TV;
 	constexpr int ITEMS = setop_items((int) sizeof(TK));
 	constexpr unsigned TILE = (unsigned) setop_tile((int) sizeof(TK));
-	constexpr bool VALS = MODE == SETOP_V4 || MODE == SETOP_V8;
+	constexpr bool VALS = MODE == CLO_OP_V4 || MODE == CLO_OP_V8;
 	static_assert(TILE <= 65536u, "slots are 16-bit");
 	__shared__ __attribute__((aligned(16))) TK s_keys[TILE];
-	__shared__ unsigned short s_slot[MODE == SETOP_KEYS ? 1 : TILE];
+	__shared__ unsigned short s_slot[MODE == CLO_OP_KEYS ? 1 : TILE];
 	__shared__ __attribute__((aligned(16))) TV s_vals[VALS ? TILE : 1];
 	__shared__ unsigned s_g[4], s_wave[SETOP_WAVES];
 	const unsigned tid = threadIdx.x;
-	const setop_range r = setop_tile_range<TILE>(split, na, nb);
+	const clo_op_range r = clo_op_tile_range<TILE>(split, na, nb);
 	const bool keeps_b = op == CLO_HIP_SETOP_UNION || op == CLO_HIP_SETOP_SYMMETRIC_DIFFERENCE;
 	bool nbr_ok;
 	const TK nbr = setop_neighbour<TK>(ka, kb, na, nb, r, kx, tid, nbr_ok);
 
-	setop_stage<TK, true>(ka + r.a0, r.na_t, s_keys, kx, tid);
-	setop_stage<TK, true>(kb + r.b0, r.nb_t, s_keys + r.na_t, kx, tid);
+	clo_op_stage<TK, true>(ka + r.a0, r.na_t, s_keys, kx, tid);
+	clo_op_stage<TK, true>(kb + r.b0, r.nb_t, s_keys + r.na_t, kx, tid);
 	if constexpr (VALS) {   // requested now, needed after the merge; no element of B leaves an intersection or a difference
-		setop_stage<TV, false>(va + r.a0, r.na_t, s_vals, kx, tid);
-		if (keeps_b) setop_stage<TV, false>(vb + r.b0, r.nb_t, s_vals + r.na_t, kx, tid);
+		clo_op_stage<TV, false>(va + r.a0, r.na_t, s_vals, kx, tid);
+		if (keeps_b) clo_op_stage<TV, false>(vb + r.b0, r.nb_t, s_vals + r.na_t, kx, tid);
 	}
 	__syncthreads();
 	TK out[ITEMS];
@@ -367,19 +287,19 @@ void clo_setop_apply_kernel(const TK* __restrict__ ka, const typename setop_val<
 	for (int i = 0; i < ITEMS; ++i) {
 		if (keep >> i & 1u) {   // at < kept <= cnt
 			s_keys[at] = clo_keyx_inv<TK>(out[i], kx);
-			if constexpr (MODE != SETOP_KEYS) s_slot[at] = (unsigned short) slot[i];
+			if constexpr (MODE != CLO_OP_KEYS) s_slot[at] = (unsigned short) slot[i];
 			++at;
 		}
 	}
 	__syncthreads();
 	// the tile's rows land at [off, off + kept) of the outputs; nothing is stored at or above the capacity
 	const unsigned off = offset[blockIdx.x];
-	const unsigned rows = off < cap ? setop_min(kept, cap - off) : 0u;
-	if (kout) setop_store<TK>(kout + off, rows, tid, [&](unsigned j) { return s_keys[j]; });
-	if constexpr (VALS) setop_store<TV>(vout + off, rows, tid, [&](unsigned j) { return s_vals[s_slot[j]]; });
-	if constexpr (MODE == SETOP_ARG) {
+	const unsigned rows = off < cap ? clo_op_min(kept, cap - off) : 0u;
+	if (kout) clo_op_store<TK>(kout + off, rows, tid, [&](unsigned j) { return s_keys[j]; });
+	if constexpr (VALS) clo_op_store<TV>(vout + off, rows, tid, [&](unsigned j) { return s_vals[s_slot[j]]; });
+	if constexpr (MODE == CLO_OP_ARG) {
 		const unsigned base_b = na + r.b0 - r.na_t;   // slot s >= na_t is B[b0 + s - na_t], index na + b0 + s - na_t of A || B (mod 2^32: exact)
-		setop_store<TV>(vout + off, rows, tid, [&](unsigned j) { const unsigned s = s_slot[j]; return s < r.na_t ? r.a0 + s : base_b + s; });
+		clo_op_store<TV>(vout + off, rows, tid, [&](unsigned j) { const unsigned s = s_slot[j]; return s < r.na_t ? r.a0 + s : base_b + s; });
 	}
 }
 
@@ -427,22 +347,19 @@ int setop_launch(const setop_args& a) {
 template <typename TK>
 int setop_dispatch(const setop_args& a, int mode) {
 	switch (mode) {
-		case SETOP_KEYS: return setop_launch<TK, SETOP_KEYS>(a);
-		case SETOP_V4: return setop_launch<TK, SETOP_V4>(a);
-		case SETOP_V8: return setop_launch<TK, SETOP_V8>(a);
-		default: return setop_launch<TK, SETOP_ARG>(a);
+		case CLO_OP_KEYS: return setop_launch<TK, CLO_OP_KEYS>(a);
+		case CLO_OP_V4: return setop_launch<TK, CLO_OP_V4>(a);
+		case CLO_OP_V8: return setop_launch<TK, CLO_OP_V8>(a);
+		default: return setop_launch<TK, CLO_OP_ARG>(a);
 	}
 }
-
-inline bool setop_key_size_ok(int ks) { return ks == 1 || ks == 2 || ks == 4 || ks == 8; }
-inline bool setop_value_size_ok(int vs) { return vs == 0 || vs == 4 || vs == 8; }
 
 }  // namespace
 
 extern "C" {
 
 size_t clo_hip_setop_tile(int key_size, int value_size) {
-	if (!setop_key_size_ok(key_size) || !setop_value_size_ok(value_size)) return 0;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size)) return 0;
 	return setop_tile(key_size);
 }
 
@@ -450,8 +367,7 @@ size_t clo_hip_setop_workspace_bytes(size_t numel_a, size_t numel_b) {
 	const size_t n = numel_a + numel_b;
 	if (n == 0 || n < numel_a) return 0;
 	// tiles + 1 split points and tiles counts of 4 bytes for the smallest tile, in whole CLO_HIP_WORKSPACE_ALIGN units
-	const size_t bytes = (2 * ((n + SETOP_MIN_TILE - 1) / SETOP_MIN_TILE) + 1) * sizeof(unsigned);
-	return (bytes + CLO_HIP_WORKSPACE_ALIGN - 1) / CLO_HIP_WORKSPACE_ALIGN * CLO_HIP_WORKSPACE_ALIGN;
+	return clo_op_ws_align((2 * ((n + SETOP_MIN_TILE - 1) / SETOP_MIN_TILE) + 1) * sizeof(unsigned));
 }
 
 int clo_hip_setop(int op, const void* keys_a, const void* values_a, size_t numel_a, const void* keys_b, const void* values_b, size_t numel_b,
@@ -459,7 +375,7 @@ int clo_hip_setop(int op, const void* keys_a, const void* values_a, size_t numel
 	void* workspace, size_t workspace_bytes, void* stream) {
 	if (op < CLO_HIP_SETOP_UNION || op > CLO_HIP_SETOP_SYMMETRIC_DIFFERENCE) return CLO_HIP_EARGS;
 	if (key_kind < 0 || key_kind > 2) return CLO_HIP_EARGS;
-	if (!setop_key_size_ok(key_size) || !setop_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
 	if (numel_a > 0xffffffffull || numel_b > 0xffffffffull || numel_a + numel_b > 0xffffffffull) return CLO_HIP_EARGS;
 	if ((numel_a > 0 && !keys_a) || (numel_b > 0 && !keys_b)) return CLO_HIP_EARGS;
 	if (!num_out || clo_misaligned(num_out, 8)) return CLO_HIP_EARGS;
@@ -492,13 +408,8 @@ int clo_hip_setop(int op, const void* keys_a, const void* values_a, size_t numel
 	a.na = (unsigned) numel_a; a.nb = (unsigned) numel_b; a.cap = (unsigned) cap; a.op = op;
 	a.kx = clo_keyx_make(key_kind, 0, 8 * key_size);
 	a.ws = (unsigned*) workspace; a.num_out = (unsigned long long*) num_out; a.s = (hipStream_t) stream;
-	const int mode = value_size == 0 ? SETOP_KEYS : arg ? SETOP_ARG : value_size == 4 ? SETOP_V4 : SETOP_V8;
-	switch (key_size) {
-		case 1: return setop_dispatch<uint8_t>(a, mode);
-		case 2: return setop_dispatch<uint16_t>(a, mode);
-		case 4: return setop_dispatch<uint32_t>(a, mode);
-		default: return setop_dispatch<uint64_t>(a, mode);
-	}
+	const int mode = clo_op_mode(value_size, arg);
+	return clo_op_by_key_size(key_size, [&](auto tk) { return setop_dispatch<decltype(tk)>(a, mode); });
 }
 
 }  // extern "C"

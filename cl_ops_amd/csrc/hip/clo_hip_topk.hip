@@ -28,6 +28,7 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
+#include "clo_hip_op_device.h"
 
 namespace {
 
@@ -35,6 +36,7 @@ constexpr int TOPK_THREADS = 256;
 constexpr int TOPK_WAVES = TOPK_THREADS / 64;
 constexpr int TOPK_VEC = 4;
 constexpr int TOPK_ROW_ELEMS = TOPK_THREADS * TOPK_VEC;   // 1024
+static_assert(TOPK_THREADS == CLO_OP_THREADS && TOPK_VEC == CLO_OP_VEC, "the shared helpers' work-group and vector");
 constexpr unsigned TOPK_SCAN_ITEMS = 8;                   // the scan sweeps TOPK_THREADS * TOPK_SCAN_ITEMS tiles per trip
 static_assert(TOPK_THREADS * TOPK_SCAN_ITEMS == CLO_HIP_TOPK_SCAN_TRIP, "the header names the scan's trip");
 constexpr int TOPK_DIGIT_BITS = 8;
@@ -49,9 +51,9 @@ constexpr unsigned TOPK_SORTED_MAX = 4096;                // (x, row) of 8-byte 
 constexpr int topk_rows(int key_size, int value_size) { return (key_size > value_size ? key_size : value_size) <= 4 ? 8 : 4; }
 constexpr size_t topk_tile(int key_size, int value_size) { return (size_t) topk_rows(key_size, value_size) * TOPK_ROW_ELEMS; }
 
-enum { TOPK_KEYS = 0, TOPK_V4 = 1, TOPK_V8 = 2, TOPK_ARG = 3 };
-template <int MODE> struct topk_val { typedef uint32_t T; static constexpr int size = MODE == TOPK_KEYS ? 0 : 4; };
-template <> struct topk_val<TOPK_V8> { typedef unsigned long long T; static constexpr int size = 8; };
+// the modes CLO_OP_KEYS, V4, V8 and ARG (clo_hip_op_device.h); the table keeps a name of its own here because the
+// kernels' symbols spell it
+template <int MODE> struct topk_val : clo_op_val<MODE> {};
 
 // What PICK hands on: the digits found so far (right-aligned) and the remaining 0-based rank among the keys that
 // share them. state[p] is read by digit sweep p and by PICK p; state[passes] = (T, r) by COUNT and APPLY.
@@ -63,30 +65,6 @@ constexpr size_t TOPK_WS_STATES = 256;                                    // 9 s
 constexpr size_t TOPK_WS_SORTKEYS = (size_t) TOPK_SORTED_MAX * 8;         // the compacted keys of a "sorted" call without keys_out
 constexpr size_t TOPK_WS_COUNTS = TOPK_WS_TABLES + TOPK_WS_STATES + TOPK_WS_SORTKEYS;
 static_assert(sizeof(topk_state) == 16 && 9 * sizeof(topk_state) <= TOPK_WS_STATES, "the states fit");
-
-__device__ __forceinline__ unsigned topk_min(unsigned a, unsigned b) { return a < b ? a : b; }
-
-// Four consecutive elements from element index i0 (a multiple of 4) of an array of n: one vector load where the array's
-// start allows it (vec_ok) and all four exist, else one by one; elements past the end read as 0. (sel_load4.)
-template <typename T>
-__device__ __forceinline__ void topk_load4(const T* __restrict__ p, size_t i0, size_t n, bool vec_ok, T (&v)[TOPK_VEC]) {
-	if (vec_ok && i0 + TOPK_VEC <= n) {
-		if constexpr (sizeof(T) == 8) {
-			typedef T vec2 __attribute__((ext_vector_type(2)));
-			const vec2 a = *reinterpret_cast<const vec2*>(p + i0), b = *reinterpret_cast<const vec2*>(p + i0 + 2);
-			v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-		} else {
-			typedef T vec4 __attribute__((ext_vector_type(4)));
-			const vec4 x = *reinterpret_cast<const vec4*>(p + i0);
-			v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-		}
-	} else {
-		#pragma unroll
-		for (int c = 0; c < TOPK_VEC; ++c) v[c] = i0 + c < n ? p[i0 + c] : (T) 0;
-	}
-}
-template <typename T>
-inline int topk_vec_ok(const void* p) { return !clo_misaligned(p, sizeof(T) * TOPK_VEC < 16 ? sizeof(T) * TOPK_VEC : 16); }
 
 // x of a key: the order-key function of merge, search and select, complemented for "largest"
 template <typename TK, int KIND>
@@ -121,7 +99,7 @@ void clo_topk_digit_kernel(const TK* __restrict__ keys, size_t n, unsigned tiles
 		const size_t base = (size_t) tile * TILE + (size_t) tid * TOPK_VEC;
 		TK k[ROWS][TOPK_VEC];
 		#pragma unroll
-		for (int r = 0; r < ROWS; ++r) topk_load4<TK>(keys, base + (size_t) r * TOPK_ROW_ELEMS, n, kvec != 0, k[r]);
+		for (int r = 0; r < ROWS; ++r) clo_op_load4<TK>(keys, base + (size_t) r * TOPK_ROW_ELEMS, n, kvec != 0, k[r]);
 		#pragma unroll
 		for (int r = 0; r < ROWS; ++r) {
 			#pragma unroll
@@ -192,7 +170,7 @@ void clo_topk_count_kernel(const TK* __restrict__ keys, size_t n, int rows, TK f
 	for (int r0 = 0; r0 < rows; r0 += 4) {   // rows is 4 or 8
 		TK k[4][TOPK_VEC];
 		#pragma unroll
-		for (int r = 0; r < 4; ++r) topk_load4<TK>(keys, base + (size_t) (r0 + r) * TOPK_ROW_ELEMS, n, kvec != 0, k[r]);
+		for (int r = 0; r < 4; ++r) clo_op_load4<TK>(keys, base + (size_t) (r0 + r) * TOPK_ROW_ELEMS, n, kvec != 0, k[r]);
 		#pragma unroll
 		for (int r = 0; r < 4; ++r) {
 			#pragma unroll
@@ -218,7 +196,7 @@ void clo_topk_count_kernel(const TK* __restrict__ keys, size_t n, int rows, TK f
 }
 
 // ---- 4. count scan: blockIdx.x 0 scans lt, 1 scans eq: count[0, tiles) -> exclusive sums in place, count[tiles] = the
-// sum of all. One work-group each; select's scan. ----
+// sum of all. One work-group each; the plain form of select's scan, which requests its counts a trip ahead. ----
 __global__ __launch_bounds__(TOPK_THREADS)
 void clo_topk_scan_kernel(unsigned* __restrict__ lt, unsigned* __restrict__ eq, unsigned tiles) {
 	constexpr unsigned TRIP = TOPK_THREADS * TOPK_SCAN_ITEMS;
@@ -258,28 +236,6 @@ void clo_topk_scan_kernel(unsigned* __restrict__ lt, unsigned* __restrict__ eq, 
 	if (tid == 0) count[tiles] = carry;
 }
 
-// dst[i] = get(i) for i in [0, count): lanes on adjacent 16-byte vectors from dst's first 16-byte boundary on, the
-// fewer than two vectors' worth before and after it element by element. (sel_store.)
-template <typename T, typename F>
-__device__ __forceinline__ void topk_store(T* __restrict__ dst, unsigned count, unsigned tid, F get) {
-	constexpr unsigned PER = 16u / sizeof(T);
-	typedef T vec __attribute__((ext_vector_type(PER)));
-	const unsigned head = topk_min((unsigned) ((16u - ((uintptr_t) dst & 15u)) & 15u) / (unsigned) sizeof(T), count);
-	const unsigned nvec = (count - head) / PER, body_end = head + nvec * PER;
-	for (unsigned v = tid; v < nvec; v += TOPK_THREADS) {
-		const unsigned i0 = head + v * PER;
-		vec x;
-		#pragma unroll
-		for (unsigned c = 0; c < PER; ++c) x[c] = get(i0 + c);
-		*reinterpret_cast<vec*>(dst + i0) = x;
-	}
-	const unsigned rest = head + (count - body_end);   // fewer than 2 PER <= 32 elements
-	if (tid < rest) {
-		const unsigned i = tid < head ? tid : body_end + (tid - head);
-		dst[i] = get(i);
-	}
-}
-
 // One scan of the tile in input order (row, wave, lane, element): at[r] becomes the number of set bits of the tile before
 // this lane's four elements of row r; returns the tile's total. s_piece: ROWS * TOPK_WAVES words.
 template <int ROWS>
@@ -314,8 +270,8 @@ void clo_topk_apply_kernel(const TK* __restrict__ keys, const typename topk_val<
 	typedef typename topk_val<MODE>::T TV;
 	constexpr int ROWS = topk_rows((int) sizeof(TK), topk_val<MODE>::size);
 	constexpr unsigned TILE = (unsigned) ROWS * TOPK_ROW_ELEMS;
-	constexpr bool VALS = MODE == TOPK_V4 || MODE == TOPK_V8;
-	constexpr size_t ELEM = MODE != TOPK_KEYS && sizeof(TV) > sizeof(TK) ? sizeof(TV) : sizeof(TK);
+	constexpr bool VALS = MODE == CLO_OP_V4 || MODE == CLO_OP_V8;
+	constexpr size_t ELEM = MODE != CLO_OP_KEYS && sizeof(TV) > sizeof(TK) ? sizeof(TV) : sizeof(TK);
 	__shared__ __attribute__((aligned(16))) unsigned char s_buf[TILE * ELEM];
 	__shared__ unsigned s_piece[ROWS * TOPK_WAVES];
 	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = (unsigned) __builtin_amdgcn_readfirstlane((int) (tid >> 6));
@@ -333,8 +289,8 @@ void clo_topk_apply_kernel(const TK* __restrict__ keys, const typename topk_val<
 	#pragma unroll
 	for (int r = 0; r < ROWS; ++r) {
 		const size_t i0 = base + (size_t) r * TOPK_ROW_ELEMS;
-		topk_load4<TK>(keys, i0, n, kvec != 0, k[r]);
-		if constexpr (VALS) topk_load4<TV>(values, i0, n, vvec != 0, v[r]);
+		clo_op_load4<TK>(keys, i0, n, kvec != 0, k[r]);
+		if constexpr (VALS) clo_op_load4<TV>(values, i0, n, vvec != 0, v[r]);
 		bits[r] = 0u; eqb[r] = 0u;
 		#pragma unroll
 		for (int c = 0; c < TOPK_VEC; ++c) {
@@ -388,14 +344,14 @@ void clo_topk_apply_kernel(const TK* __restrict__ keys, const typename topk_val<
 			}
 		}
 		__syncthreads();
-		topk_store(out + (size_t) keep_at, keep_rows, tid, [&](unsigned j) { return s[j]; });
+		clo_op_store(out + (size_t) keep_at, keep_rows, tid, [&](unsigned j) { return s[j]; });
 	};
 	if (want_keys) {
 		compact(reinterpret_cast<TK*>(s_buf), kout, [&](int r, int c, unsigned) { return k[r][c]; });
-		if constexpr (MODE != TOPK_KEYS) __syncthreads();   // the values take the keys' place
+		if constexpr (MODE != CLO_OP_KEYS) __syncthreads();   // the values take the keys' place
 	}
 	if constexpr (VALS) compact(reinterpret_cast<TV*>(s_buf), vout, [&](int r, int c, unsigned) { return v[r][c]; });
-	if constexpr (MODE == TOPK_ARG) compact(reinterpret_cast<TV*>(s_buf), vout, [&](int, int, unsigned idx) { return (TV) (tile_start + idx); });
+	if constexpr (MODE == CLO_OP_ARG) compact(reinterpret_cast<TV*>(s_buf), vout, [&](int, int, unsigned idx) { return (TV) (tile_start + idx); });
 }
 
 // ---- 6. "sorted": rows [0, m), m <= TOPK_SORTED_MAX, sorted by (x, row) in LDS by one work-group, in place. ksrc: the
@@ -404,7 +360,7 @@ void clo_topk_apply_kernel(const TK* __restrict__ keys, const typename topk_val<
 template <typename TK, int VS>
 __global__ __launch_bounds__(TOPK_SORT_THREADS)
 void clo_topk_sort_kernel(const TK* ksrc, TK* kout, void* vout_, unsigned m, TK flip, int key_kind) {
-	typedef typename topk_val<VS == 8 ? TOPK_V8 : TOPK_V4>::T TV;
+	typedef typename topk_val<VS == 8 ? CLO_OP_V8 : CLO_OP_V4>::T TV;
 	constexpr unsigned PER = TOPK_SORTED_MAX / TOPK_SORT_THREADS;
 	__shared__ TK s_x[TOPK_SORTED_MAX];
 	__shared__ unsigned s_row[TOPK_SORTED_MAX];
@@ -438,7 +394,7 @@ void clo_topk_sort_kernel(const TK* ksrc, TK* kout, void* vout_, unsigned m, TK 
 		#pragma unroll
 		for (unsigned c = 0; c < PER; ++c) {
 			const unsigned j = tid + c * TOPK_SORT_THREADS;
-			v[c] = j < m ? vout[topk_min(s_row[j], m - 1u)] : (TV) 0;
+			v[c] = j < m ? vout[clo_op_min(s_row[j], m - 1u)] : (TV) 0;
 		}
 		__syncthreads();   // every gather has returned before a row is overwritten
 		#pragma unroll
@@ -477,7 +433,7 @@ int topk_find(const topk_args& a, TK flip) {
 	const unsigned tiles = (unsigned) ((a.n + TILE - 1) / TILE);
 	size_t groups = topk_sweep_groups();
 	if (groups > tiles) groups = tiles;
-	const int kvec = topk_vec_ok<TK>(a.keys);
+	const int kvec = clo_op_vec_ok<TK>(a.keys);
 	const hipError_t e = hipMemsetAsync(tables, 0, (size_t) PASSES * TOPK_DIGITS * sizeof(unsigned), a.s);
 	if (e != hipSuccess) return (int) e;
 	for (int p = 0; p < PASSES; ++p) {
@@ -518,7 +474,7 @@ int topk_launch(const topk_args& a) {
 	const unsigned tiles = (unsigned) ((a.n + TILE - 1) / TILE);
 	unsigned* const lt = reinterpret_cast<unsigned*>(a.ws + TOPK_WS_COUNTS);
 	unsigned* const eq = lt + (tiles + 1u);
-	const int kvec = topk_vec_ok<TK>(a.keys), vvec = topk_vec_ok<TV>(a.values);
+	const int kvec = clo_op_vec_ok<TK>(a.keys), vvec = clo_op_vec_ok<TV>(a.values);
 	// a "sorted" call without keys_out: the sort reads the compacted keys from the workspace
 	TK* const kdst = a.kout ? (TK*) a.kout : a.sorted ? reinterpret_cast<TK*>(a.ws + TOPK_WS_TABLES + TOPK_WS_STATES) : nullptr;
 	{
@@ -546,10 +502,10 @@ int topk_launch(const topk_args& a) {
 template <typename TK, int KIND>
 int topk_dispatch_mode(const topk_args& a, int mode) {
 	switch (mode) {
-		case TOPK_KEYS: return topk_launch<TK, KIND, TOPK_KEYS>(a);
-		case TOPK_V4: return topk_launch<TK, KIND, TOPK_V4>(a);
-		case TOPK_V8: return topk_launch<TK, KIND, TOPK_V8>(a);
-		default: return topk_launch<TK, KIND, TOPK_ARG>(a);
+		case CLO_OP_KEYS: return topk_launch<TK, KIND, CLO_OP_KEYS>(a);
+		case CLO_OP_V4: return topk_launch<TK, KIND, CLO_OP_V4>(a);
+		case CLO_OP_V8: return topk_launch<TK, KIND, CLO_OP_V8>(a);
+		default: return topk_launch<TK, KIND, CLO_OP_ARG>(a);
 	}
 }
 
@@ -562,22 +518,19 @@ int topk_dispatch(const topk_args& a, int mode) {
 	return topk_dispatch_mode<TK, 0>(a, mode);
 }
 
-inline bool topk_key_size_ok(int ks) { return ks == 1 || ks == 2 || ks == 4 || ks == 8; }
-inline bool topk_value_size_ok(int vs) { return vs == 0 || vs == 4 || vs == 8; }
-
 }  // namespace
 
 extern "C" {
 
 size_t clo_hip_topk_tile(int key_size, int value_size) {
-	if (!topk_key_size_ok(key_size) || !topk_value_size_ok(value_size)) return 0;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size)) return 0;
 	return topk_tile(key_size, value_size);
 }
 
 size_t clo_hip_topk_sweep_groups(void) { return topk_sweep_groups(); }
 
 size_t clo_hip_topk_sorted_max(int key_size, int value_size) {
-	if (!topk_key_size_ok(key_size) || !topk_value_size_ok(value_size)) return 0;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size)) return 0;
 	return TOPK_SORTED_MAX;
 }
 
@@ -585,8 +538,7 @@ size_t clo_hip_topk_workspace_bytes(size_t numel, int key_size, int value_size) 
 	const size_t tile = clo_hip_topk_tile(key_size, value_size);
 	if (numel == 0 || tile == 0) return 0;
 	// the digit tables, the states, the sort's keys; then two counts per tile and the two totals, 4 bytes each
-	const size_t bytes = ((numel - 1) / tile + 2) * 2 * sizeof(unsigned);
-	return TOPK_WS_COUNTS + (bytes + CLO_HIP_WORKSPACE_ALIGN - 1) / CLO_HIP_WORKSPACE_ALIGN * CLO_HIP_WORKSPACE_ALIGN;
+	return TOPK_WS_COUNTS + clo_op_ws_align(((numel - 1) / tile + 2) * 2 * sizeof(unsigned));
 }
 
 int clo_hip_topk(int which, int order, const void* keys_in, const void* values_in, void* keys_out, void* values_out, void* kth_out,
@@ -594,7 +546,7 @@ int clo_hip_topk(int which, int order, const void* keys_in, const void* values_i
 	if (which != CLO_HIP_TOPK_SMALLEST && which != CLO_HIP_TOPK_LARGEST) return CLO_HIP_EARGS;
 	if (order != CLO_HIP_TOPK_INPUT && order != CLO_HIP_TOPK_SORTED) return CLO_HIP_EARGS;
 	if (key_kind < 0 || key_kind > 2) return CLO_HIP_EARGS;
-	if (!topk_key_size_ok(key_size) || !topk_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
+	if (!clo_op_key_size_ok(key_size) || !clo_op_value_size_ok(value_size) || (key_kind == 2 && key_size == 1)) return CLO_HIP_EUNSUPPORTED;
 	if (numel > 0xffffffffull) return CLO_HIP_EARGS;
 	if (!keys_out && !values_out && !kth_out) return CLO_HIP_EARGS;
 	if (value_size == 0 && (values_in || values_out)) return CLO_HIP_EARGS;
@@ -614,13 +566,8 @@ int clo_hip_topk(int which, int order, const void* keys_in, const void* values_i
 	a.keys = keys_in; a.values = values_in; a.kout = keys_out; a.vout = values_out; a.kth = kth_out;
 	a.n = numel; a.m = (unsigned) m; a.desc = which == CLO_HIP_TOPK_LARGEST; a.sorted = order == CLO_HIP_TOPK_SORTED; a.kind = key_kind;
 	a.ws = (unsigned char*) workspace; a.s = (hipStream_t) stream;
-	const int mode = value_size == 0 ? TOPK_KEYS : arg ? TOPK_ARG : value_size == 4 ? TOPK_V4 : TOPK_V8;
-	switch (key_size) {
-		case 1: return topk_dispatch<uint8_t>(a, mode);
-		case 2: return topk_dispatch<uint16_t>(a, mode);
-		case 4: return topk_dispatch<uint32_t>(a, mode);
-		default: return topk_dispatch<uint64_t>(a, mode);
-	}
+	const int mode = clo_op_mode(value_size, arg);
+	return clo_op_by_key_size(key_size, [&](auto tk) { return topk_dispatch<decltype(tk)>(a, mode); });
 }
 
 }  // extern "C"
