@@ -4,6 +4,7 @@
 #ifndef CLO_INTERNAL_H
 #define CLO_INTERNAL_H
 
+#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -228,7 +229,10 @@ CLO_INTERNAL CCLEvent* clo_op_end_command(CCLQueue* cq, CCLEvent* evt, int st, c
  * slot, blocking transfers on cq_comm. The first failure is kept in `err` and every later step does nothing, so a
  * driver writes the steps one after the other and asks once, at clo_stage_close. In between it makes its device call
  * itself: `if (clo_stage_ok(&st)) st.evt = clo_x_with_device_data(..., st.cq_exec, st.cq_comm, st.dev[..], &st.err);`
- * — the first read-back then waits for st.evt. A slot whose host pointer is NULL or that holds 0 bytes stays NULL. */
+ * — the first read-back then waits for st.evt. A slot whose host pointer is NULL or that holds 0 bytes stays NULL.
+ * write_name / read_name (NULL after clo_stage_open; the sorts and the scan of clo_sort_abstract.c and
+ * clo_scan_abstract.c set them): the uploads / the read-backs are enqueued non-blocking, their events carry that name
+ * for a CCLProf consumer, and they are waited for with ccl_event_wait, which also asks the queue's give-up watch. */
 #define CLO_STAGE_SLOTS 8
 typedef struct {
 	CCLContext* ctx;
@@ -238,6 +242,8 @@ typedef struct {
 	CCLBuffer* dev[CLO_STAGE_SLOTS];
 	CCLEvent* evt;           /* the device call's event, until the first read has waited for it */
 	CCLEventWaitList ewl;
+	const char* write_name;
+	const char* read_name;
 	GError* err;
 } clo_stage;
 CLO_INTERNAL void clo_stage_open(clo_stage* st, CCLContext* ctx, CCLQueue* cq_exec, CCLQueue* cq_comm);
@@ -247,5 +253,40 @@ CLO_INTERNAL void clo_stage_out(clo_stage* st, int slot, const void* host, size_
 CLO_INTERNAL void clo_stage_read(clo_stage* st, int slot, void* host, size_t bytes);        /* the first bytes of the slot */
 /* Moves the failure, if any, to *err; releases the buffers and the queue made here. CL_TRUE if nothing failed. */
 CLO_INTERNAL cl_bool clo_stage_close(clo_stage* st, GError** err);
+
+/* ---- What the pipelined host-data paths share (clo_host_pipe.c): scan_with_host_data_pipelined of clo_scan_abstract.c
+ * and clo_sort_satradix_host_pipeline of clo_sort_satradix.c keep the arithmetic that says where item k lies. ---- */
+
+/* The copy-out helper. A copy to pageable host memory holds the calling thread for its duration, so the items of a
+ * pipeline (the chunks of a scan, the buckets of a sort) go back to the host on a thread of their own. It waits until
+ * item k is posted, calls copy(user, k) — which brings item k to the host and returns a clo_hip status — and counts the
+ * item completed. The first failure is kept and ends the helper; an item that was never posted is never copied. A
+ * zeroed clo_drain is one that was never started. */
+typedef struct {
+	pthread_t thread;
+	pthread_mutex_t mtx;
+	pthread_cond_t cv;
+	int (*copy)(void* user, size_t k);
+	void* user;
+	size_t count, posted, completed;   /* items in all / handed to / finished by the helper */
+	int device, started, abort, status;
+} clo_drain;
+#define CLO_DRAIN_START "pthread_create"   /* what a failed clo_drain_start is called in the caller's error */
+/* Reads the current device for the helper and creates it: 0 or a clo_hip status. */
+CLO_INTERNAL int clo_drain_start(clo_drain* d, size_t count, int (*copy)(void* user, size_t k), void* user);
+/* Items 0 .. k - 1 may be copied now. */
+CLO_INTERNAL void clo_drain_post(clo_drain* d, size_t k);
+/* Returns once k items are completed, or as soon as one has failed: 0, or the first failure's status. */
+CLO_INTERNAL int clo_drain_wait(clo_drain* d, size_t k);
+/* Ends and joins the helper (items posted by then are still copied). Does nothing after a failed or missing start, or
+ * when called again. */
+CLO_INTERNAL void clo_drain_stop(clo_drain* d);
+
+/* The runtime calls of one item going out — wait for `ready`, copy `bytes` (if any) on s_out, wait for s_out — and of one
+ * chunk coming in: copy on s_in, record `arrived` there, make s_exec wait for it. 0 or a clo_hip status. */
+CLO_INTERNAL int clo_pipe_copy_out(void* ready, void* host, const void* dev, size_t bytes, void* s_out);
+CLO_INTERNAL int clo_pipe_upload(void* dev, const void* host, size_t bytes, void* s_in, void* arrived, void* s_exec);
+/* The stream the chunks come in on: cq_comm's, or `own` when the caller gave one queue for everything. */
+CLO_INTERNAL void* clo_pipe_transfer_stream(CCLQueue* cq_comm, void* s_exec, void* own);
 
 #endif

@@ -88,21 +88,31 @@ void clo_stage_open(clo_stage* st, CCLContext* ctx, CCLQueue* cq_exec, CCLQueue*
 	st->cq_comm = cq_comm ? cq_comm : cq_exec;
 }
 
+/* One transfer of a slot on cq_comm: blocking, or — under a name — enqueued, named and waited for with ccl_event_wait. */
+static void stage_copy(clo_stage* st, int slot, int read, const char* name, size_t bytes, void* host, CCLEventWaitList* after) {
+	CCLEvent* e = (read ? ccl_buffer_enqueue_read : ccl_buffer_enqueue_write)(st->dev[slot], st->cq_comm, name ? CL_FALSE : CL_TRUE,
+		0, bytes, host, after, &st->err);
+	if (!name || st->err) return;
+	ccl_event_set_name(e, name);
+	ccl_event_wait(ccl_ewl(&st->ewl, e, NULL), &st->err);
+}
+
+/* (a named transfer is never left out: an empty array still gets its buffer and its named copy, as upstream's path does) */
 void clo_stage_out(clo_stage* st, int slot, const void* host, size_t bytes) {
-	if (st->err || !host || bytes == 0) return;
+	if (st->err || (!st->read_name && (!host || bytes == 0))) return;
 	st->dev[slot] = ccl_buffer_new(st->ctx, CL_MEM_READ_WRITE, bytes, NULL, &st->err);
 }
 
 void clo_stage_in(clo_stage* st, int slot, const void* host, size_t bytes) {
-	clo_stage_out(st, slot, host, bytes);
-	if (st->err || !st->dev[slot]) return;
-	ccl_buffer_enqueue_write(st->dev[slot], st->cq_comm, CL_TRUE, 0, bytes, (void*) host, NULL, &st->err);
+	if (st->err || (!st->write_name && (!host || bytes == 0))) return;
+	st->dev[slot] = ccl_buffer_new(st->ctx, CL_MEM_READ_WRITE, bytes, NULL, &st->err);
+	if (!st->err && st->dev[slot]) stage_copy(st, slot, 0, st->write_name, bytes, (void*) host, NULL);
 }
 
 void clo_stage_read(clo_stage* st, int slot, void* host, size_t bytes) {
-	if (st->err || !st->dev[slot] || bytes == 0) return;
+	if (st->err || !st->dev[slot] || (bytes == 0 && !st->read_name)) return;
 	/* the first read waits for the device call and blocks; the later ones find it done */
-	ccl_buffer_enqueue_read(st->dev[slot], st->cq_comm, CL_TRUE, 0, bytes, host, st->evt ? ccl_ewl(&st->ewl, st->evt, NULL) : NULL, &st->err);
+	stage_copy(st, slot, 1, st->read_name, bytes, host, st->evt ? ccl_ewl(&st->ewl, st->evt, NULL) : NULL);
 	st->evt = NULL;
 }
 

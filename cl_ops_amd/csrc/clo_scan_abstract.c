@@ -9,7 +9,6 @@
 #include "clo_scan.h"
 #include "clo_internal.h"
 
-#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -93,7 +92,7 @@ CloScan* clo_scan_new(const char* type, const char* options, CCLContext* ctx,
 
 		if (clo_type_sizeof(elem_type) == 0 || clo_type_sizeof(sum_type) == 0) {
 			clo_gerror_set(err, CLO_ERROR, CLO_ERROR_UNKNOWN_TYPE, "Unknown element or sum type");
-			goto error_handler;
+			goto fail;
 		}
 		/* Every pair of types is scanned, as upstream's generic kernel does (clo_scan_abstract.c:122-125):
 		 * integer sums at least as wide as integer elements by the single-pass kernel, everything else —
@@ -102,10 +101,10 @@ CloScan* clo_scan_new(const char* type, const char* options, CCLContext* ctx,
 		 * (clo_hip_fscan.hip; clo_hip_scan_is_typed decides). */
 
 		const char* token = scanner->impl_def.init(scanner, options, &err_internal);
-		if (err_internal) { clo_gerror_propagate(err, err_internal); goto error_handler; }
+		if (err_internal) { clo_gerror_propagate(err, err_internal); goto fail; }
 		if (!token) {
 			clo_gerror_set(err, CLO_ERROR, CLO_ERROR_LIBRARY, "Scan implementation '%s' failed to initialise", type);
-			goto error_handler;
+			goto fail;
 		}
 		scanner->prg = ccl_program_new_token(ctx, token, compiler_opts);
 		scan_warmup(scanner);
@@ -118,7 +117,7 @@ CloScan* clo_scan_new(const char* type, const char* options, CCLContext* ctx,
 	}
 	return scanner;
 
-error_handler:
+fail:
 	if (scanner) {
 		if (scanner->data) scanner->impl_def.finalize(scanner);
 		ccl_context_unref(scanner->ctx);
@@ -218,40 +217,21 @@ static scan_pipe_res* scan_pipe_res_get(CloScan* scanner, size_t chunk, size_t e
 }
 
 typedef struct {
-	int device;
 	scan_pipe_res* r;
 	char* out_host;
 	size_t sum_size, chunk, numel;
-	pthread_mutex_t mtx;
-	pthread_cond_t cv;
-	size_t posted, completed;    /* chunks handed to / finished by the helper */
-	int abort, status;
 } scan_pipe;
 
-static void* scan_pipe_copy_out(void* arg) {
-	scan_pipe* p = (scan_pipe*) arg;
-	clo_hip_set_device(p->device);
-	for (size_t k = 0; ; ++k) {
-		pthread_mutex_lock(&p->mtx);
-		while (p->posted <= k && !p->abort) pthread_cond_wait(&p->cv, &p->mtx);
-		const int stop = p->posted <= k;   /* aborted, or nothing more will come */
-		pthread_mutex_unlock(&p->mtx);
-		if (stop) break;
-		const size_t off = k * p->chunk;
-		const size_t cnt = p->numel - off < p->chunk ? p->numel - off : p->chunk;
-		int st = clo_hip_event_synchronize(p->r->scan_done[k & 1]);
-		if (st == 0) st = clo_hip_memcpy_d2h_async(p->out_host + off * p->sum_size, p->r->out_dev[k & 1], cnt * p->sum_size, p->r->s_out);
-		if (st == 0) st = clo_hip_stream_synchronize(p->r->s_out);
-		pthread_mutex_lock(&p->mtx);
-		if (st != 0 && p->status == 0) p->status = st;
-		p->completed = k + 1;
-		pthread_cond_broadcast(&p->cv);
-		pthread_mutex_unlock(&p->mtx);
-		if (off + cnt >= p->numel) break;
-	}
-	return NULL;
+/* Chunk k of the drain (clo_internal.h): where it lies on the device and on the host. */
+static int scan_pipe_copy_out(void* user, size_t k) {
+	const scan_pipe* p = (const scan_pipe*) user;
+	const size_t off = k * p->chunk;
+	const size_t cnt = p->numel - off < p->chunk ? p->numel - off : p->chunk;
+	return clo_pipe_copy_out(p->r->scan_done[k & 1], p->out_host + off * p->sum_size, p->r->out_dev[k & 1], cnt * p->sum_size, p->r->s_out);
 }
 
+/* The helper thread, the choice of the transfer stream and the upload of a chunk are clo_host_pipe.c's (clo_drain,
+ * clo_pipe_*: clo_internal.h), shared with the sort's pipeline in clo_sort_satradix.c. */
 static cl_bool scan_with_host_data_pipelined(CloScan* scanner, CCLQueue* cq_exec, CCLQueue* cq_comm,
 	const void* data_in, void* data_out, size_t numel, GError** err) {
 
@@ -260,57 +240,39 @@ static cl_bool scan_with_host_data_pipelined(CloScan* scanner, CCLQueue* cq_exec
 	const size_t nchunks = (numel + chunk - 1) / chunk;
 	void* s_in = ccl_queue_get_stream(cq_comm);
 	void* s_exec = ccl_queue_get_stream(cq_exec);
-	scan_pipe p;
-	pthread_t helper;
-	int helper_started = 0, st = 0;
+	scan_pipe p = { NULL, (char*) data_out, ss, chunk, numel };
+	clo_drain drain = { .started = 0 };
+	int st = 0;
 	cl_bool ok = CL_FALSE;
 	const char* what = "pipeline resources (hipMalloc / hipStreamCreate)";
 
-	memset(&p, 0, sizeof(p));
-	pthread_mutex_init(&p.mtx, NULL);
-	pthread_cond_init(&p.cv, NULL);
-	p.sum_size = ss; p.chunk = chunk; p.numel = numel; p.out_host = (char*) data_out;
-	if (clo_hip_get_device(&p.device) != 0) p.device = 0;
 	scan_pipe_res* r = scan_pipe_res_get(scanner, chunk, es, ss, &st);
 	if (!r) goto finish;
 	p.r = r;
-	if (s_in == s_exec) s_in = r->s_in_own;
+	s_in = clo_pipe_transfer_stream(cq_comm, s_exec, r->s_in_own);
 	what = "hipMemsetAsync";
 	st = clo_hip_memset_async(r->carry, 0, 2 * sizeof(uint64_t), s_exec);
 	if (st != 0) goto finish;
-	if (pthread_create(&helper, NULL, scan_pipe_copy_out, &p) != 0) { st = CLO_HIP_EARGS; what = "pthread_create"; goto finish; }
-	helper_started = 1;
+	what = CLO_DRAIN_START;
+	if ((st = clo_drain_start(&drain, nchunks, scan_pipe_copy_out, &p)) != 0) goto finish;
 
 	for (size_t k = 0; k < nchunks; ++k) {
 		const int slot = (int) (k & 1);
 		const size_t off = k * chunk;
 		const size_t cnt = numel - off < chunk ? numel - off : chunk;
-		if (k >= 2) {   /* the slot's buffers are free once chunk k-2 is back on the host */
-			pthread_mutex_lock(&p.mtx);
-			while (p.completed < k - 1 && p.status == 0) pthread_cond_wait(&p.cv, &p.mtx);
-			st = p.status;
-			pthread_mutex_unlock(&p.mtx);
-			if (st != 0) { what = "copy out"; goto finish; }
-		}
+		what = "copy out";   /* the slot's buffers are free once chunk k-2 is back on the host */
+		if (k >= 2 && (st = clo_drain_wait(&drain, k - 1)) != 0) goto finish;
 		what = "hipMemcpyAsync(h2d)";
-		st = clo_hip_memcpy_h2d_async(r->in_dev[slot], (const char*) data_in + off * es, cnt * es, s_in);
-		if (st == 0) st = clo_hip_event_record(r->in_done[slot], s_in);
-		if (st == 0) st = clo_hip_stream_wait_event(s_exec, r->in_done[slot]);
+		st = clo_pipe_upload(r->in_dev[slot], (const char*) data_in + off * es, cnt * es, s_in, r->in_done[slot], s_exec);
 		if (st != 0) goto finish;
 		if (!scanner->ext->scan_chunk(scanner, cq_exec, r->in_dev[slot], r->out_dev[slot], cnt,
 			(char*) r->carry + slot * sizeof(uint64_t), (char*) r->carry + (slot ^ 1) * sizeof(uint64_t), err)) goto finish;
 		what = "hipEventRecord";
 		st = clo_hip_event_record(r->scan_done[slot], s_exec);
 		if (st != 0) goto finish;
-		pthread_mutex_lock(&p.mtx);
-		p.posted = k + 1;
-		pthread_cond_broadcast(&p.cv);
-		pthread_mutex_unlock(&p.mtx);
+		clo_drain_post(&drain, k + 1);
 	}
-	pthread_mutex_lock(&p.mtx);
-	while (p.completed < nchunks && p.status == 0) pthread_cond_wait(&p.cv, &p.mtx);
-	st = p.status;
-	pthread_mutex_unlock(&p.mtx);
+	st = clo_drain_wait(&drain, nchunks);
 	what = "copy out";
 	ok = st == 0;
 	/* every chunk is back on the host, so every scan has completed: did one of
@@ -318,92 +280,42 @@ static cl_bool scan_with_host_data_pipelined(CloScan* scanner, CCLQueue* cq_exec
 	if (ok && scanner->ext->check_status && !scanner->ext->check_status(scanner, cq_exec, err)) ok = CL_FALSE;
 
 finish:
-	if (helper_started) {
-		pthread_mutex_lock(&p.mtx);
-		p.abort = 1;
-		pthread_cond_broadcast(&p.cv);
-		pthread_mutex_unlock(&p.mtx);
-		pthread_join(helper, NULL);
-	}
+	clo_drain_stop(&drain);
 	if (st != 0 && (err == NULL || *err == NULL)) clo_hip_failed(st, err, what);
 	if (!ok) {   /* leave nothing of this call in flight */
 		if (s_in) clo_hip_stream_synchronize(s_in);
 		clo_hip_stream_synchronize(s_exec);
 	}
-	pthread_mutex_destroy(&p.mtx);
-	pthread_cond_destroy(&p.cv);
 	return ok && (err == NULL || *err == NULL);
 }
 
-/* ref: clo_scan_abstract.c:255-362 */
+/* ref: clo_scan_abstract.c:255-362, on the named stage of clo_internal.h: the two copies are upstream's clo_scan_write
+ * and clo_scan_read to a CCLProf consumer. */
 cl_bool clo_scan_with_host_data(CloScan* scanner, CCLQueue* cq_exec, CCLQueue* cq_comm,
 	void* data_in, void* data_out, size_t numel, size_t lws_max, GError** err) {
 
 	clo_return_val_if_fail(scanner != NULL, CL_FALSE);
 	clo_return_val_if_fail(err == NULL || *err == NULL, CL_FALSE);
 
-	cl_bool status = CL_FALSE;
-	CCLEvent* evt = NULL;
-	CCLBuffer* data_in_dev = NULL;
-	CCLBuffer* data_out_dev = NULL;
-	CCLQueue* intern_queue = NULL;
-	CCLEventWaitList ewl = NULL;
-	GError* err_internal = NULL;
-	const size_t data_in_size = numel * clo_type_sizeof(scanner->elem_type);
-	const size_t data_out_size = numel * clo_type_sizeof(scanner->sum_type);
+	const clo_scan_impl_ext* ext = scanner->ext;
+	clo_stage st;
+	clo_stage_open(&st, scanner->ctx, cq_exec, cq_comm);
+	st.write_name = "clo_scan_write";
+	st.read_name = "clo_scan_read";
 
-	if (cq_exec == NULL) {
-		CCLDevice* dev = ccl_context_get_device(scanner->ctx, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		intern_queue = ccl_queue_new(scanner->ctx, dev, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		cq_exec = intern_queue;
-	}
-	if (cq_comm == NULL) cq_comm = cq_exec;
-
-	if (scanner->ext != NULL && scanner->ext->scan_chunk != NULL && !clo_hip_scan_is_typed((int) scanner->elem_type, (int) scanner->sum_type) && numel >= CLO_SCAN_PIPE_MIN_NUMEL && ccl_queue_get_stream(cq_exec) != NULL) {
-		status = scan_with_host_data_pipelined(scanner, cq_exec, cq_comm, data_in, data_out, numel, &err_internal);
-		if (err_internal) goto error_handler;
-		goto finish;
+	if (clo_stage_ok(&st) && ext != NULL && ext->scan_chunk != NULL && !clo_hip_scan_is_typed((int) scanner->elem_type, (int) scanner->sum_type) && numel >= CLO_SCAN_PIPE_MIN_NUMEL && ccl_queue_get_stream(st.cq_exec) != NULL) {
+		const cl_bool status = scan_with_host_data_pipelined(scanner, st.cq_exec, st.cq_comm, data_in, data_out, numel, &st.err);
+		return clo_stage_close(&st, err) && status;
 	}
 
-	data_in_dev = ccl_buffer_new(scanner->ctx, CL_MEM_READ_ONLY, data_in_size, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	data_out_dev = ccl_buffer_new(scanner->ctx, CL_MEM_READ_WRITE, data_out_size, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-
-	evt = ccl_buffer_enqueue_write(data_in_dev, cq_comm, CL_FALSE, 0, data_in_size, data_in, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	ccl_event_set_name(evt, "clo_scan_write");
-	ccl_event_wait(ccl_ewl(&ewl, evt, NULL), &err_internal);
-	if (err_internal) goto error_handler;
-
-	evt = scanner->impl_def.scan_with_device_data(scanner, cq_exec, cq_comm, data_in_dev, data_out_dev,
-		numel, lws_max, &err_internal);
-	if (err_internal) goto error_handler;
-
-	evt = ccl_buffer_enqueue_read(data_out_dev, cq_comm, CL_FALSE, 0, data_out_size, data_out,
-		evt ? ccl_ewl(&ewl, evt, NULL) : NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	ccl_event_set_name(evt, "clo_scan_read");
-	ccl_event_wait(ccl_ewl(&ewl, evt, NULL), &err_internal);
-	if (err_internal) goto error_handler;
+	clo_stage_in(&st, 0, data_in, numel * clo_type_sizeof(scanner->elem_type));
+	clo_stage_out(&st, 1, data_out, numel * clo_type_sizeof(scanner->sum_type));
+	if (clo_stage_ok(&st))
+		st.evt = scanner->impl_def.scan_with_device_data(scanner, st.cq_exec, st.cq_comm, st.dev[0], st.dev[1], numel, lws_max, &st.err);
+	clo_stage_read(&st, 1, data_out, numel * clo_type_sizeof(scanner->sum_type));
 	/* the result is on the host: it is only good if no look-back spin gave up */
-	if (scanner->ext && scanner->ext->check_status && !scanner->ext->check_status(scanner, cq_exec, &err_internal)) goto error_handler;
-
-	status = CL_TRUE;
-	goto finish;
-
-error_handler:
-	clo_gerror_propagate(err, err_internal);
-	status = CL_FALSE;
-
-finish:
-	ccl_event_wait_list_clear(&ewl);
-	if (data_in_dev) ccl_buffer_destroy(data_in_dev);
-	if (data_out_dev) ccl_buffer_destroy(data_out_dev);
-	if (intern_queue) ccl_queue_destroy(intern_queue);
-	return status;
+	if (clo_stage_ok(&st) && ext && ext->check_status) ext->check_status(scanner, st.cq_exec, &st.err);
+	return clo_stage_close(&st, err);
 }
 
 /* ---- getters, ref: clo_scan_abstract.c:372-569 ---- */

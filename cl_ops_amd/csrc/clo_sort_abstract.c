@@ -285,7 +285,7 @@ CloSort* clo_sort_new(const char* type, const char* options, CCLContext* ctx,
 		ks->key_kind = clo_type_key_kind(sorter->key_type);
 		if (ks->elem_size == 0 || ks->key_size == 0) {
 			clo_gerror_set(err, CLO_ERROR, CLO_ERROR_UNKNOWN_TYPE, "Unknown element or key type");
-			goto error_handler;
+			goto fail;
 		}
 		const int key_ok = parse_get_key(get_key, ks->elem_size, ks->key_size, &ks->key_shift, &ks->key_bits)
 			&& !(ks->key_kind == 2 && ks->key_bits != 8 * ks->key_size)   /* a float key is the whole key type */
@@ -317,7 +317,7 @@ CloSort* clo_sort_new(const char* type, const char* options, CCLContext* ctx,
 					compiler_opts ? " with options '" : "", compiler_opts ? compiler_opts : "", compiler_opts ? "'" : "",
 					clo_hip_error_string(st), log ? "\n" : "", log ? log : "");
 				free(log);
-				goto error_handler;
+				goto fail;
 			}
 			free(log);
 			ks->key_shift = 0;
@@ -326,10 +326,10 @@ CloSort* clo_sort_new(const char* type, const char* options, CCLContext* ctx,
 		}
 
 		const char* token = sorter->impl_def.init(sorter, options, &err_internal);
-		if (err_internal) { clo_gerror_propagate(err, err_internal); goto error_handler; }
+		if (err_internal) { clo_gerror_propagate(err, err_internal); goto fail; }
 		if (!token) {
 			clo_gerror_set(err, CLO_ERROR, CLO_ERROR_LIBRARY, "Sort implementation '%s' failed to initialise", type);
-			goto error_handler;
+			goto fail;
 		}
 		/* No JIT: the "program" is a token naming the ahead-of-time kernels. */
 		sorter->prg = ccl_program_new_token(ctx, token, compiler_opts);
@@ -343,7 +343,7 @@ CloSort* clo_sort_new(const char* type, const char* options, CCLContext* ctx,
 	}
 	return sorter;
 
-error_handler:
+fail:
 	if (sorter) {
 		/* finalize only what init created */
 		if (sorter->jit) { if (sorter->jit_is_radix) clo_hip_radix_jit_destroy(sorter->jit); else clo_hip_bitonic_jit_destroy(sorter->jit); }
@@ -372,99 +372,41 @@ CCLEvent* clo_sort_with_device_data(CloSort* sorter, CCLQueue* cq_exec, CCLQueue
 	return sorter->impl_def.sort_with_device_data(sorter, cq_exec, cq_comm, data_in, data_out, numel, lws_max, err);
 }
 
-/* ref: clo_sort_abstract.c:296-418 — buffers, blocking H2D on cq_comm, sort on
- * cq_exec, blocking D2H of the result. */
+/* ref: clo_sort_abstract.c:296-418 — buffers, H2D on cq_comm, sort on cq_exec, D2H of the result, on the named
+ * stage of clo_internal.h: the two copies are upstream's clo_sort_write and clo_sort_read to a CCLProf consumer. */
 cl_bool clo_sort_with_host_data(CloSort* sorter, CCLQueue* cq_exec, CCLQueue* cq_comm,
 	void* data_in, void* data_out, size_t numel, size_t lws_max, GError** err) {
 
 	clo_return_val_if_fail(sorter != NULL, CL_FALSE);
 	clo_return_val_if_fail(err == NULL || *err == NULL, CL_FALSE);
 
-	cl_bool status = CL_FALSE;
-	CCLBuffer* data_in_dev = NULL;
-	CCLBuffer* data_aux_dev = NULL;
-	CCLBuffer* data_out_dev = NULL;
-	CCLBuffer* data_read_dev = NULL;
-	CCLQueue* intern_queue = NULL;
-	CCLEvent* evt = NULL;
-	CCLEventWaitList ewl = NULL;
-	GError* err_internal = NULL;
 	const size_t data_size = numel * clo_type_sizeof(sorter->elem_type);
-	CCLContext* ctx = sorter->ctx;
-
-	if (cq_exec == NULL) {
-		CCLDevice* dev = ccl_context_get_device(ctx, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		intern_queue = ccl_queue_new(ctx, dev, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		cq_exec = intern_queue;
-	}
-	if (cq_comm == NULL) cq_comm = cq_exec;
+	const clo_sort_impl_ext* ext = clo_sort_impl_ext_find(sorter->impl_def.name);
+	const int in_place = sorter->impl_def.in_place != 0;   /* then the input buffer is sorted and read back: no second one */
+	clo_stage st;
+	clo_stage_open(&st, sorter->ctx, cq_exec, cq_comm);
+	st.write_name = "clo_sort_write";
+	st.read_name = "clo_sort_read";
 
 	/* Transfers overlapped with the sort where the implementation knows how (satradix on large
 	 * arrays: clo_sort_satradix.c); the result is the blocking path's. */
-	{
-		const clo_sort_impl_ext* ext = clo_sort_impl_ext_find(sorter->impl_def.name);
+	if (clo_stage_ok(&st) && ext && ext->host_pipeline) {
 		int handled = 0;
-		if (ext && ext->host_pipeline) {
-			status = ext->host_pipeline(sorter, cq_exec, cq_comm, data_in, data_out, numel, &handled, &err_internal);
-			if (handled) {
-				if (err_internal) goto error_handler;
-				goto finish;
-			}
-			status = CL_FALSE;
-		}
+		const cl_bool status = ext->host_pipeline(sorter, st.cq_exec, st.cq_comm, data_in, data_out, numel, &handled, &st.err);
+		if (handled) return clo_stage_close(&st, err) && status;
 	}
 
-	data_in_dev = ccl_buffer_new(ctx, CL_MEM_READ_ONLY, data_size, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	if (!sorter->impl_def.in_place) {
-		data_aux_dev = ccl_buffer_new(ctx, CL_MEM_WRITE_ONLY, data_size, NULL, &err_internal);
-		if (err_internal) goto error_handler;
-		data_out_dev = data_aux_dev;
-		data_read_dev = data_aux_dev;
-	} else {
-		data_read_dev = data_in_dev;
-	}
-
-	evt = ccl_buffer_enqueue_write(data_in_dev, cq_comm, CL_FALSE, 0, data_size, data_in, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	ccl_event_set_name(evt, "clo_sort_write");
-	ccl_event_wait(ccl_ewl(&ewl, evt, NULL), &err_internal);
-	if (err_internal) goto error_handler;
-
-	evt = sorter->impl_def.sort_with_device_data(sorter, cq_exec, cq_comm, data_in_dev, data_out_dev,
-		numel, lws_max, &err_internal);
-	if (err_internal) goto error_handler;
-
-	evt = ccl_buffer_enqueue_read(data_read_dev, cq_comm, CL_FALSE, 0, data_size, data_out,
-		evt ? ccl_ewl(&ewl, evt, NULL) : NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	ccl_event_set_name(evt, "clo_sort_read");
-	ccl_event_wait(ccl_ewl(&ewl, evt, NULL), &err_internal);
-	if (err_internal) goto error_handler;
+	clo_stage_in(&st, 0, data_in, data_size);
+	if (!in_place) clo_stage_out(&st, 1, data_out, data_size);
+	if (clo_stage_ok(&st))
+		st.evt = sorter->impl_def.sort_with_device_data(sorter, st.cq_exec, st.cq_comm, st.dev[0], st.dev[1], numel, lws_max, &st.err);
+	clo_stage_read(&st, in_place ? 0 : 1, data_out, data_size);
 	/* A sorter whose kernels poll other work-groups may have given up a bounded
 	 * spin: asked here explicitly, whatever queues the caller passed (with a
 	 * separate cq_comm — upstream's own harness, benchmarks/clo_sort_bench.c:160-162 —
 	 * the wait above has synchronised with the transfer queue only). */
-	{
-		const clo_sort_impl_ext* ext = clo_sort_impl_ext_find(sorter->impl_def.name);
-		if (ext && ext->check_status && !ext->check_status(sorter, cq_exec, &err_internal)) goto error_handler;
-	}
-
-	status = CL_TRUE;
-	goto finish;
-
-error_handler:
-	clo_gerror_propagate(err, err_internal);
-	status = CL_FALSE;
-
-finish:
-	ccl_event_wait_list_clear(&ewl);
-	if (data_in_dev) ccl_buffer_destroy(data_in_dev);
-	if (data_aux_dev) ccl_buffer_destroy(data_aux_dev);
-	if (intern_queue) ccl_queue_destroy(intern_queue);
-	return status;
+	if (clo_stage_ok(&st) && ext && ext->check_status) ext->check_status(sorter, st.cq_exec, &st.err);
+	return clo_stage_close(&st, err);
 }
 
 /* ---- sorting by key (not upstream; include/clo_sort.h) ---- */
@@ -514,59 +456,22 @@ cl_bool clo_sort_by_key_with_host_data(CloSort* sorter, CCLQueue* cq_exec, CCLQu
 	}
 	if (numel == 0) return CL_TRUE;
 
-	cl_bool status = CL_FALSE;
-	CCLBuffer* dev[4] = { NULL, NULL, NULL, NULL };   /* keys in, values in, keys out, values out */
-	CCLQueue* intern_queue = NULL;
-	CCLEvent* evt = NULL;
-	CCLEventWaitList ewl = NULL;
-	GError* err_internal = NULL;
+	/* keys in, values in, keys out, values out. The copies keep the names the buffer calls give them; the read-backs
+	 * are waited for like the plain sort's, so the transfer queue's give-up watch is asked here too. */
 	const size_t kbytes = numel * (size_t) sorter->spec.elem_size, vbytes = numel * sizeof(cl_uint);
-	const size_t bytes[4] = { kbytes, vbytes, kbytes, vbytes };
-	const int used[4] = { 1, values_in != NULL, keys_out != NULL, 1 };
-	CCLContext* ctx = sorter->ctx;
-
-	if (cq_exec == NULL) {
-		CCLDevice* d = ccl_context_get_device(ctx, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		intern_queue = ccl_queue_new(ctx, d, 0, &err_internal);
-		if (err_internal) goto error_handler;
-		cq_exec = intern_queue;
-	}
-	if (cq_comm == NULL) cq_comm = cq_exec;
-	for (int i = 0; i < 4; ++i) {
-		if (!used[i]) continue;
-		dev[i] = ccl_buffer_new(ctx, CL_MEM_READ_WRITE, bytes[i], NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	ccl_buffer_enqueue_write(dev[0], cq_comm, CL_TRUE, 0, kbytes, (void*) keys_in, NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	if (values_in) {
-		ccl_buffer_enqueue_write(dev[1], cq_comm, CL_TRUE, 0, vbytes, (void*) values_in, NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	evt = clo_sort_by_key_with_device_data(sorter, cq_exec, cq_comm, dev[0], dev[1], dev[2], dev[3], numel, lws_max, &err_internal);
-	if (err_internal) goto error_handler;
-	evt = ccl_buffer_enqueue_read(dev[3], cq_comm, CL_FALSE, 0, vbytes, values_out, evt ? ccl_ewl(&ewl, evt, NULL) : NULL, &err_internal);
-	if (err_internal) goto error_handler;
-	if (keys_out) {
-		evt = ccl_buffer_enqueue_read(dev[2], cq_comm, CL_FALSE, 0, kbytes, keys_out, NULL, &err_internal);
-		if (err_internal) goto error_handler;
-	}
-	ccl_event_wait(ccl_ewl(&ewl, evt, NULL), &err_internal);
-	if (err_internal) goto error_handler;
-	if (ext->check_status && !ext->check_status(sorter, cq_exec, &err_internal)) goto error_handler;
-	status = CL_TRUE;
-	goto finish;
-
-error_handler:
-	clo_gerror_propagate(err, err_internal);
-	status = CL_FALSE;
-
-finish:
-	ccl_event_wait_list_clear(&ewl);
-	for (int i = 0; i < 4; ++i) if (dev[i]) ccl_buffer_destroy(dev[i]);
-	if (intern_queue) ccl_queue_destroy(intern_queue);
-	return status;
+	clo_stage st;
+	clo_stage_open(&st, sorter->ctx, cq_exec, cq_comm);
+	st.read_name = "read_buffer";
+	clo_stage_in(&st, 0, keys_in, kbytes);
+	clo_stage_in(&st, 1, values_in, vbytes);
+	if (keys_out) clo_stage_out(&st, 2, keys_out, kbytes);
+	clo_stage_out(&st, 3, values_out, vbytes);
+	if (clo_stage_ok(&st))
+		st.evt = clo_sort_by_key_with_device_data(sorter, st.cq_exec, st.cq_comm, st.dev[0], st.dev[1], st.dev[2], st.dev[3], numel, lws_max, &st.err);
+	clo_stage_read(&st, 3, values_out, vbytes);
+	clo_stage_read(&st, 2, keys_out, kbytes);
+	if (clo_stage_ok(&st) && ext->check_status) ext->check_status(sorter, st.cq_exec, &st.err);
+	return clo_stage_close(&st, err);
 }
 
 /* ---- getters, ref: clo_sort_abstract.c:428-629 ---- */

@@ -304,9 +304,10 @@ static cl_bool clo_sort_satradix_check_status(CloSort* sorter, CCLQueue* cq, GEr
  * the time at 2^28. Hence the default: pipelined, UNLESS cq_exec was created with
  * CL_QUEUE_PROFILING_ENABLE — a caller who profiles the exec queue is timing "the sort" and gets
  * the one sort upstream would run. CLO_SORT_HOST_PIPELINE=0 / 1 in the environment overrides.
+ *
+ * The helper thread, the choice of the transfer stream and the upload of a chunk are clo_host_pipe.c's (clo_drain,
+ * clo_pipe_*: clo_internal.h), shared with the scan's pipeline in clo_scan_abstract.c.
  * --------------------------------------------------------------------------- */
-#include <pthread.h>
-
 #ifndef SAT_PIPE_MIN_NUMEL   /* (the sanitizer build of tests/hoststub shrinks it) */
 #define SAT_PIPE_MIN_NUMEL ((size_t) 1 << 24)
 #endif
@@ -335,14 +336,10 @@ typedef struct sat_pipe_res_s {
 } sat_pipe_res;
 
 typedef struct {
-	int device;
 	sat_pipe_res* r;
 	char* out_host;
 	size_t es;
 	size_t off[SAT_PIPE_BUCKETS + 1];      /* where bucket b starts in the result (elements) */
-	pthread_mutex_t mtx;
-	pthread_cond_t cv;
-	int posted, completed, abort, status;
 } sat_pipe;
 
 static int satradix_segments_apply(CloSort* sorter);
@@ -361,26 +358,11 @@ static void sat_pipe_res_free(sat_pipe_res* r) {
 	free(r);
 }
 
-static void* sat_pipe_copy_out(void* arg) {
-	sat_pipe* p = (sat_pipe*) arg;
-	clo_hip_set_device(p->device);
-	for (int b = 0; b < SAT_PIPE_BUCKETS; ++b) {
-		pthread_mutex_lock(&p->mtx);
-		while (p->posted <= b && !p->abort) pthread_cond_wait(&p->cv, &p->mtx);
-		const int stop = p->posted <= b;
-		pthread_mutex_unlock(&p->mtx);
-		if (stop) break;
-		const size_t cnt = p->off[b + 1] - p->off[b];
-		int st = clo_hip_event_synchronize(p->r->sorted[b]);
-		if (st == 0 && cnt) st = clo_hip_memcpy_d2h_async(p->out_host + p->off[b] * p->es, (const char*) p->r->in.ptr + p->off[b] * p->es, cnt * p->es, p->r->s_out);
-		if (st == 0) st = clo_hip_stream_synchronize(p->r->s_out);
-		pthread_mutex_lock(&p->mtx);
-		if (st != 0 && p->status == 0) p->status = st;
-		p->completed = b + 1;
-		pthread_cond_broadcast(&p->cv);
-		pthread_mutex_unlock(&p->mtx);
-	}
-	return NULL;
+/* Bucket b of the drain (clo_internal.h): it lies where it belongs in the result, on the device as on the host. */
+static int sat_pipe_copy_out(void* user, size_t b) {
+	const sat_pipe* p = (const sat_pipe*) user;
+	return clo_pipe_copy_out(p->r->sorted[b], p->out_host + p->off[b] * p->es, (const char*) p->r->in.ptr + p->off[b] * p->es,
+		(p->off[b + 1] - p->off[b]) * p->es, p->r->s_out);
 }
 
 static cl_bool clo_sort_satradix_host_pipeline(CloSort* sorter, CCLQueue* cq_exec, CCLQueue* cq_comm, const void* data_in,
@@ -411,16 +393,13 @@ static cl_bool clo_sort_satradix_host_pipeline(CloSort* sorter, CCLQueue* cq_exe
 	const int nchunks = (int) ((numel + chunk - 1) / chunk);
 	uint64_t counts[SAT_PIPE_CHUNKS][SAT_PIPE_SUBS];   /* [chunk][sub-bucket]: `subs` entries of a row are used */
 	sat_pipe p;
-	pthread_t helper;
-	int helper_started = 0, st = 0;
+	clo_drain drain = { .started = 0 };
+	int st = 0;
 	cl_bool ok = CL_FALSE;
 	CCLEvent* evt = NULL;
 	const char* what = "pipeline resources (hipMalloc / hipStreamCreate)";
 
 	memset(&p, 0, sizeof(p));
-	pthread_mutex_init(&p.mtx, NULL);
-	pthread_cond_init(&p.cv, NULL);
-	if (clo_hip_get_device(&p.device) != 0) p.device = 0;
 	sat_pipe_res* r = data->pipe;
 	if (!r) {
 		r = data->pipe = (sat_pipe_res*) calloc(1, sizeof(*r));
@@ -442,17 +421,14 @@ static cl_bool clo_sort_satradix_host_pipeline(CloSort* sorter, CCLQueue* cq_exe
 	}
 	if (st != 0) goto finish;
 	p.r = r; p.out_host = (char*) data_out; p.es = (size_t) es;
-	void* s_in = ccl_queue_get_stream(cq_comm);
-	if (s_in == s_exec) s_in = r->s_in;
+	void* s_in = clo_pipe_transfer_stream(cq_comm, s_exec, r->s_in);
 
 	/* ---- copy in, every chunk split as soon as it is there ---- */
 	for (int c = 0; c < nchunks; ++c) {
 		const size_t off = (size_t) c * chunk;
 		const size_t cnt = numel - off < chunk ? numel - off : chunk;
 		what = "hipMemcpyAsync(h2d)";
-		st = clo_hip_memcpy_h2d_async((char*) r->in.ptr + off * es, (const char*) data_in + off * es, cnt * es, s_in);
-		if (st == 0) st = clo_hip_event_record(r->in_done[c], s_in);
-		if (st == 0) st = clo_hip_stream_wait_event(s_exec, r->in_done[c]);
+		st = clo_pipe_upload((char*) r->in.ptr + off * es, (const char*) data_in + off * es, cnt * es, s_in, r->in_done[c], s_exec);
 		if (st != 0) goto finish;
 		evt = ccl_queue_begin_command(cq_exec, CLO_SORT_SATRADIX_KNAME_HISTOGRAM, err);
 		if (!evt) goto finish;
@@ -501,8 +477,8 @@ static cl_bool clo_sort_satradix_host_pipeline(CloSort* sorter, CCLQueue* cq_exe
 		int h = 0;
 		if (!clo_sort_satradix_reserve_segments(sorter, cq_exec, largest, per, &h, err)) goto finish;
 	}
-	if (pthread_create(&helper, NULL, sat_pipe_copy_out, &p) != 0) { st = CLO_HIP_EARGS; what = "pthread_create"; goto finish; }
-	helper_started = 1;
+	what = CLO_DRAIN_START;
+	if ((st = clo_drain_start(&drain, SAT_PIPE_BUCKETS, sat_pipe_copy_out, &p)) != 0) goto finish;
 
 	/* ---- bucket by bucket: gather its pieces in chunk order, sort it where it belongs, hand it to the copy out ---- */
 	for (int b = 0; b < SAT_PIPE_BUCKETS; ++b) {
@@ -557,36 +533,22 @@ static cl_bool clo_sort_satradix_host_pipeline(CloSort* sorter, CCLQueue* cq_exe
 		if (!ccl_queue_end_command(cq_exec, evt, err)) { ccl_queue_abort_command(cq_exec, evt); goto finish; }
 		what = "hipEventRecord";
 		if ((st = clo_hip_event_record(r->sorted[b], s_exec)) != 0) goto finish;
-		pthread_mutex_lock(&p.mtx);
-		p.posted = b + 1;
-		pthread_cond_broadcast(&p.cv);
-		pthread_mutex_unlock(&p.mtx);
+		clo_drain_post(&drain, (size_t) b + 1);
 	}
-	pthread_mutex_lock(&p.mtx);
-	while (p.completed < SAT_PIPE_BUCKETS && p.status == 0) pthread_cond_wait(&p.cv, &p.mtx);
-	st = p.status;
-	pthread_mutex_unlock(&p.mtx);
+	st = clo_drain_wait(&drain, SAT_PIPE_BUCKETS);
 	what = "copy out";
 	ok = st == 0;
 	/* every bucket is back on the host, so every sort has completed: did one give up a look-back spin? */
 	if (ok && !clo_sort_satradix_check_status(sorter, cq_exec, err)) ok = CL_FALSE;
 
 finish:
-	if (helper_started) {
-		pthread_mutex_lock(&p.mtx);
-		p.abort = 1;
-		pthread_cond_broadcast(&p.cv);
-		pthread_mutex_unlock(&p.mtx);
-		pthread_join(helper, NULL);
-	}
+	clo_drain_stop(&drain);
 	if (st != 0 && (err == NULL || *err == NULL)) clo_hip_failed(st, err, what);
 	if (!ok) {   /* leave nothing of this call in flight */
 		if (r && r->s_in) clo_hip_stream_synchronize(r->s_in);
 		clo_hip_stream_synchronize(ccl_queue_get_stream(cq_comm));
 		clo_hip_stream_synchronize(s_exec);
 	}
-	pthread_mutex_destroy(&p.mtx);
-	pthread_cond_destroy(&p.cv);
 	if (r && r->in.bytes > SAT_PIPE_KEEP_BYTES) {   /* large arrays: do not leave two more copies of them resident in the sorter */
 		clo_hip_stream_synchronize(s_exec);
 		clo_devbuf_release(&r->in);

@@ -6,6 +6,9 @@
  *   3. the sharded sort (clo_shard.c) with G = 1 (loopback), 2, 4, 8 ranks as THREADS of this process over an
  *      in-memory transport: count exchange, slices, pieces, segmented sorts, growth of the receive buffers, and the
  *      ranks failing together (arguments; memory)
+ *   4. the sharded sort's bounded waits
+ *   5. the blocking host-data calls below the pipelines' thresholds: the names their copies carry on a profiling queue
+ *   6. the copy-out helper of the two pipelines by itself (clo_drain of clo_internal.h): order, failures, stops
  * Results are checked against qsort / a serial scan. Exit code 0 = everything right.
  * Built by tests/test_host_sanitizers.py with -fsanitize=address,undefined and with -fsanitize=thread, with the
  * size thresholds of the pipelines shrunk (-DSAT_PIPE_MIN_NUMEL=... etc.) so that a run takes seconds.
@@ -21,6 +24,7 @@
 
 #include "cl_ops.h"
 #include "clo_hip.h"
+#include "clo_internal.h"
 #include "clo_shard.h"
 
 static int failures;
@@ -411,6 +415,159 @@ static int fuzz_shard(int cases, uint64_t seed) {
 	return failures;
 }
 
+/* ---- 5. the blocking host-data calls and the names of their copies ----
+ * Below the pipelines' thresholds, with a profiling queue for the transfers: a CCLProf consumer sees upstream's names
+ * for the copies of a sort and of a scan; the by-key form's copies carry the names the buffer calls give them. CCLProf
+ * adds up the events of one name, so what is checked is the exact set of names on the transfer queue after each call. */
+static void expect_names(CCLQueue* qc, const char* what, const char* first, const char* second) {
+	GError* err = NULL;
+	CCLProf* prof = ccl_prof_new();
+	ccl_prof_add_queue(prof, "comm", qc);
+	CHECK(ccl_prof_calc(prof, &err), "%s: ccl_prof_calc", what);
+	report(&err, "ccl_prof_calc");
+	int seen = 0;
+	ccl_prof_iter_agg_init(prof, 0);
+	for (const CCLProfAgg* a = ccl_prof_iter_agg_next(prof); a != NULL; a = ccl_prof_iter_agg_next(prof), ++seen)
+		CHECK(strcmp(a->event_name, first) == 0 || strcmp(a->event_name, second) == 0, "%s: a copy called '%s'", what, a->event_name);
+	CHECK(seen == 2 && ccl_prof_get_agg(prof, first) != NULL && ccl_prof_get_agg(prof, second) != NULL,
+		"%s: %d names on the transfer queue, '%s' and '%s' expected", what, seen, first, second);
+	ccl_prof_destroy(prof);
+}
+
+static void test_event_names(CCLContext* ctx) {
+	enum { N = 1000 };   /* below every pipeline threshold of this build */
+	GError* err = NULL;
+	CloType ut = CLO_UINT;
+	static uint32_t keys[N], values[N], keys_out[N], values_out[N];
+	static uint64_t sums[N];
+	for (size_t i = 0; i < N; ++i) { keys[i] = (uint32_t) (rnd() % 50); values[i] = (uint32_t) i; }
+	CCLQueue* qx = ccl_queue_new(ctx, NULL, 0, &err);
+	CCLQueue* qc = ccl_queue_new(ctx, NULL, CL_QUEUE_PROFILING_ENABLE, &err);
+	CHECK(qx && qc, "queues");
+	report(&err, "ccl_queue_new");
+
+	/* satradix reads the result from a second buffer, sbitonic sorts in place and reads the input buffer back */
+	static const char* const sorters[2] = { "satradix", "sbitonic" };
+	for (int k = 0; k < 2; ++k) {
+		CloSort* s = clo_sort_new(sorters[k], NULL, ctx, &ut, NULL, NULL, NULL, NULL, &err);
+		CHECK(s != NULL, "clo_sort_new(%s)", sorters[k]);
+		report(&err, "clo_sort_new");
+		if (!s) continue;
+		memset(keys_out, 0xff, sizeof keys_out);
+		CHECK(clo_sort_with_host_data(s, qx, qc, keys, keys_out, N, 0, &err), "clo_sort_with_host_data(%s)", sorters[k]);
+		report(&err, "clo_sort_with_host_data");
+		size_t bad = 0;
+		for (size_t i = 1; i < N; ++i) bad += keys_out[i - 1] > keys_out[i];
+		CHECK(bad == 0 && keys_out[N - 1] < 50, "%s: the blocking sort's result", sorters[k]);
+		expect_names(qc, sorters[k], "clo_sort_write", "clo_sort_read");
+		if (k == 0) {
+			for (int form = 0; form < 2; ++form) {   /* keys and values in and out; argsort, values out alone */
+				memset(values_out, 0xff, sizeof values_out);
+				CHECK(clo_sort_by_key_with_host_data(s, qx, qc, keys, form ? NULL : values, form ? NULL : keys_out, values_out, N, 0, &err), "clo_sort_by_key_with_host_data");
+				report(&err, "clo_sort_by_key_with_host_data");
+				bad = 0;
+				for (size_t i = 1; i < N; ++i) bad += values_out[i] >= N || keys[values_out[i - 1]] > keys[values_out[i]];
+				CHECK(bad == 0, "the by-key sort's result");
+				expect_names(qc, form ? "argsort" : "sort by key", "write_buffer", "read_buffer");
+			}
+		}
+		clo_sort_destroy(s);
+	}
+
+	CloScan* sc = clo_scan_new("blelloch", NULL, ctx, CLO_UINT, CLO_ULONG, NULL, &err);
+	CHECK(sc != NULL, "clo_scan_new");
+	report(&err, "clo_scan_new");
+	if (sc) {
+		CHECK(clo_scan_with_host_data(sc, qx, qc, keys, sums, N, 0, &err), "clo_scan_with_host_data");
+		report(&err, "clo_scan_with_host_data");
+		uint64_t acc = 0;
+		size_t bad = 0;
+		for (size_t i = 0; i < N; ++i) { bad += sums[i] != acc; acc += keys[i]; }
+		CHECK(bad == 0, "the blocking scan's result");
+		expect_names(qc, "scan", "clo_scan_write", "clo_scan_read");
+		clo_scan_destroy(sc);
+	}
+	ccl_queue_destroy(qc);
+	ccl_queue_destroy(qx);
+}
+
+/* ---- 6. the copy-out helper by itself (clo_drain, clo_internal.h): the callbacks are the test's own ---- */
+#define DRAIN_MAX 16
+typedef struct {
+	size_t fail_at;                 /* the item whose copy fails with 700 + item, or (size_t) -1 */
+	int sleep_first;                /* the first copy sleeps, so that the poster gets ahead */
+	atomic_size_t posted;           /* what the poster is about to post */
+	atomic_int copies[DRAIN_MAX], calls, early, out_of_order;
+} drain_user;
+static int drain_copy(void* user, size_t k) {
+	drain_user* u = (drain_user*) user;
+	if (u->sleep_first && k == 0) { struct timespec ts = { 0, 20 * 1000000 }; nanosleep(&ts, NULL); }
+	if (k >= atomic_load(&u->posted)) atomic_fetch_add(&u->early, 1);
+	if (k != (size_t) atomic_fetch_add(&u->calls, 1)) atomic_fetch_add(&u->out_of_order, 1);
+	if (k < DRAIN_MAX) atomic_fetch_add(&u->copies[k], 1);
+	return k == u->fail_at ? 700 + (int) k : 0;
+}
+static void drain_post(clo_drain* d, drain_user* u, size_t k) { atomic_store(&u->posted, k); clo_drain_post(d, k); }
+/* items [0, copied) were copied once each, in order and after their post; no other item was touched */
+static void drain_expect(drain_user* u, size_t copied, const char* what) {
+	size_t bad = 0;
+	for (size_t i = 0; i < DRAIN_MAX; ++i) bad += atomic_load(&u->copies[i]) != (i < copied ? 1 : 0);
+	CHECK(bad == 0 && (size_t) atomic_load(&u->calls) == copied && atomic_load(&u->early) == 0 && atomic_load(&u->out_of_order) == 0,
+		"drain, %s: %d copies where %zu were due, %zu items with a wrong count, %d before their post, %d out of order", what,
+		atomic_load(&u->calls), copied, bad, atomic_load(&u->early), atomic_load(&u->out_of_order));
+}
+
+static void test_drain(void) {
+	static const size_t counts[3] = { 1, 2, DRAIN_MAX };
+	clo_drain d;
+	drain_user u;
+	for (int c = 0; c < 3; ++c) {   /* posted one by one: each is copied once its post has come, and not before */
+		const size_t n = counts[c];
+		memset(&u, 0, sizeof(u)); u.fail_at = (size_t) -1;
+		CHECK(clo_drain_start(&d, n, drain_copy, &u) == 0, "drain: start");
+		for (size_t k = 1; k <= n; ++k) {
+			drain_post(&d, &u, k);
+			CHECK(clo_drain_wait(&d, k) == 0, "drain: wait for %zu of %zu", k, n);
+			CHECK((size_t) atomic_load(&u.calls) == k, "drain: %d copies after %zu posts", atomic_load(&u.calls), k);
+		}
+		CHECK(clo_drain_wait(&d, n) == 0, "drain: wait for all %zu", n);
+		clo_drain_stop(&d);
+		drain_expect(&u, n, "one by one");
+	}
+	for (int c = 0; c < 6; ++c) {   /* a copy fails, first / middle / last item; posted up to the failing item only, or all at once */
+		const size_t n = DRAIN_MAX, f = c % 3 == 0 ? 0 : (c % 3 == 1 ? n / 2 : n - 1), upto = c < 3 ? f + 1 : n;
+		memset(&u, 0, sizeof(u)); u.fail_at = f;
+		CHECK(clo_drain_start(&d, n, drain_copy, &u) == 0, "drain: start");
+		drain_post(&d, &u, upto);
+		const int st = clo_drain_wait(&d, upto);
+		CHECK(st == 700 + (int) f, "drain: a failure at item %zu reported as %d", f, st);
+		clo_drain_stop(&d);   /* ends the helper although fewer than n items were posted */
+		drain_expect(&u, f + 1, "a failing copy");
+	}
+	/* stopped early, with nothing posted, twice, and never started */
+	memset(&u, 0, sizeof(u)); u.fail_at = (size_t) -1;
+	CHECK(clo_drain_start(&d, DRAIN_MAX, drain_copy, &u) == 0, "drain: start");
+	drain_post(&d, &u, 3);
+	CHECK(clo_drain_wait(&d, 3) == 0, "drain: wait for 3 of 16");
+	clo_drain_stop(&d);
+	drain_expect(&u, 3, "stopped after 3 of 16");
+	memset(&u, 0, sizeof(u)); u.fail_at = (size_t) -1;
+	CHECK(clo_drain_start(&d, DRAIN_MAX, drain_copy, &u) == 0, "drain: start");
+	clo_drain_stop(&d);
+	clo_drain_stop(&d);
+	drain_expect(&u, 0, "stopped with nothing posted, twice");
+	memset(&d, 0, sizeof(d));
+	clo_drain_stop(&d);
+	/* every item posted while the helper is still busy with the first */
+	memset(&u, 0, sizeof(u)); u.fail_at = (size_t) -1; u.sleep_first = 1;
+	CHECK(clo_drain_start(&d, DRAIN_MAX, drain_copy, &u) == 0, "drain: start");
+	drain_post(&d, &u, 1);
+	drain_post(&d, &u, DRAIN_MAX);
+	CHECK(clo_drain_wait(&d, DRAIN_MAX) == 0, "drain: wait for all, posted ahead");
+	clo_drain_stop(&d);
+	drain_expect(&u, DRAIN_MAX, "posted ahead of the helper");
+}
+
 int main(int argc, char** argv) {
 	const int quick = argc > 1 && strcmp(argv[1], "quick") == 0;
 	if (argc > 1 && strcmp(argv[1], "fuzz") == 0) {
@@ -426,7 +583,9 @@ int main(int argc, char** argv) {
 	test_host_sort(ctx, "ulong", (1u << 16) + 7, 0);
 	test_host_sort(ctx, "ulong", (1u << 16) + 1, 1);
 	test_host_scan(ctx, (1u << 18) + 77);
+	test_event_names(ctx);
 	ccl_context_destroy(ctx);
+	test_drain();
 	const size_t n = quick ? 5000 : 9000;
 	test_shard(1, 4, n * 4, "loopback=1", 0, 0, 3);
 	test_shard(1, 8, n * 2, "loopback=1,slices=8", 0, 0, 1);

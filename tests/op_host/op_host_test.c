@@ -3,8 +3,8 @@
  * CPU, over the host stubs of the thin C-ABI (tests/hoststub/*stub*.c), under AddressSanitizer + UBSan
  * (tests/test_op_host_cpu.py): range overlap and the conflict helper's order, the key kind of all eleven types, the
  * value-type predicate, the name lookup, the object head, and the staging of a host-data call — a round trip with a
- * caller's queue and with the queue made inside, and the failure on a context without a device, with err and with
- * err == NULL, after which nothing is left allocated.
+ * caller's queue and with the queue made inside, the same with named copies on a profiling queue, and the failure on a
+ * context without a device, with err and with err == NULL, without and with names, after which nothing is left allocated.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -116,8 +116,39 @@ static void test_stage_round_trip(CCLContext* ctx, CCLQueue* cq_exec, CCLQueue* 
 	CHECK(untouched[0] == 7 && untouched[3] == 7, "a read that should not have happened");
 }
 
+/* The same round trip on a stage with names, over a profiling transfer queue: the two copies reach a CCLProf consumer
+ * under those names and no other; and a named stage leaves nothing out — an empty array gets its buffer and its copies. */
+static void test_stage_names(CCLContext* ctx, CCLQueue* cq_exec, size_t bytes) {
+	GError* err = NULL;
+	const unsigned char in[7] = { 3, 1, 4, 1, 5, 9, 2 };
+	unsigned char out[7] = { 0 };
+	CCLQueue* prof_q = ccl_queue_new(ctx, NULL, CL_QUEUE_PROFILING_ENABLE, &err);
+	CHECK(prof_q != NULL && err == NULL, "a profiling queue");
+	if (!prof_q) return;
+	clo_stage st;
+	clo_stage_open(&st, ctx, cq_exec, prof_q);
+	CHECK(st.write_name == NULL && st.read_name == NULL, "a stage is opened without names");
+	st.write_name = "test_write";
+	st.read_name = "test_read";
+	clo_stage_in(&st, 0, in, bytes);
+	CHECK(clo_stage_ok(&st) && st.dev[0] != NULL && ccl_buffer_get_size(st.dev[0]) == bytes, "the named slot");
+	clo_stage_read(&st, 0, out, bytes);
+	CHECK(clo_stage_close(&st, &err) == CL_TRUE && err == NULL, "close: %s", err ? err->message : "");
+	CHECK(memcmp(out, in, bytes) == 0 && (bytes == sizeof in || out[bytes] == 0), "the bytes read back under a name");
+	CCLProf* prof = ccl_prof_new();
+	ccl_prof_add_queue(prof, "comm", prof_q);
+	CHECK(ccl_prof_calc(prof, &err) && err == NULL, "ccl_prof_calc");
+	int seen = 0;
+	ccl_prof_iter_agg_init(prof, 0);
+	while (ccl_prof_iter_agg_next(prof) != NULL) ++seen;
+	CHECK(seen == 2 && ccl_prof_get_agg(prof, "test_write") != NULL && ccl_prof_get_agg(prof, "test_read") != NULL,
+		"%d names on the transfer queue of a named stage of %zu bytes", seen, bytes);
+	ccl_prof_destroy(prof);
+	ccl_queue_destroy(prof_q);
+}
+
 /* on a context without a device and without a queue: the first step fails, the later ones do nothing, the error arrives */
-static void test_stage_failure(int with_err) {
+static void test_stage_failure(int with_err, int named) {
 	GError* err = NULL;
 	CCLContext* off = ccl_context_new_offline(&err);
 	CHECK(off != NULL && err == NULL, "offline context");
@@ -126,6 +157,7 @@ static void test_stage_failure(int with_err) {
 	clo_stage st;
 	clo_stage_open(&st, off, NULL, NULL);
 	CHECK(!clo_stage_ok(&st) && st.own_queue == NULL, "a queue on an offline context");
+	if (named) { st.write_name = "test_write"; st.read_name = "test_read"; }
 	clo_stage_in(&st, 0, bytes, 4);
 	clo_stage_out(&st, 1, out, 4);
 	clo_stage_read(&st, 1, out, 4);
@@ -173,8 +205,13 @@ int main(void) {
 	test_stage_round_trip(ctx, cq, cq2);
 	test_stage_round_trip(ctx, NULL, NULL);    /* the queue made inside, destroyed by close */
 	test_stage_round_trip(ctx, NULL, cq2);
-	test_stage_failure(1);
-	test_stage_failure(0);
+	test_stage_names(ctx, cq, 7);
+	test_stage_names(ctx, NULL, 5);
+	test_stage_names(ctx, cq, 0);
+	test_stage_failure(1, 0);
+	test_stage_failure(0, 0);
+	test_stage_failure(1, 1);
+	test_stage_failure(0, 1);
 	test_stage_late_failure(ctx, 1);
 	test_stage_late_failure(ctx, 0);
 	ccl_queue_destroy(cq2);

@@ -584,6 +584,38 @@ def test_profiler_reports_exec_queue_time(gpu):
     assert 1000 < ns < 5e9
 
 
+def test_host_data_copies_carry_their_names_on_a_profiling_transfer_queue(gpu):
+    """The blocking host-data calls name their copies for a CCLProf consumer: upstream's names for a sort and a scan,
+    the buffer calls' own for a sort by key (tests/hoststub/host_paths_test.c checks the same over the host stub)."""
+    import cl_ops_amd as clo
+    ctx, q = gpu
+    n = 4099
+    rng = np.random.default_rng(5)
+    keys = rand_u32(rng, n)
+    qc = clo.Queue(ctx, profiling=True)
+    prof = clo.Profiler(qc)
+
+    def names():
+        assert prof.duration_ns() > 0
+        return set(prof.aggregates())
+
+    s = clo.Sorter("satradix", ctx, "uint")
+    assert np.array_equal(s.with_host_data(keys, q, qc), np.sort(keys))
+    assert names() == {"clo_sort_write", "clo_sort_read"}
+    order = np.argsort(keys, kind="stable").astype(np.uint32)
+    ko, vo = s.by_key_with_host_data(keys, np.arange(n, dtype=np.uint32), q, qc)
+    assert np.array_equal(ko, keys[order]) and np.array_equal(vo, order)
+    assert names() == {"write_buffer", "read_buffer"}
+    s.close()
+    small = (keys & np.uint32(127))
+    sc = clo.Scanner("blelloch", ctx, "uint", "ulong")
+    assert np.array_equal(sc.with_host_data(small, q, qc), O.serial_scan(small, np.uint64))
+    assert names() == {"clo_scan_write", "clo_scan_read"}
+    sc.close()
+    prof.close()
+    qc.close()
+
+
 # ----------------------------------------------------------------------------
 # MSD bucket split used by the multi-GPU exchange (C-ABI: clo_hip_msd_*)
 # ----------------------------------------------------------------------------

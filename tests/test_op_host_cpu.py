@@ -3,7 +3,8 @@ stand-alone program tests/op_host/op_host_test.c checks range overlap and the or
 kind of all eleven types, the name lookup, the object head and the staging of a host-data call (round trips, and the
 failure on a context without a device with err and with err == NULL) over the host stubs of the thin C-ABI
 (tests/hoststub/*stub*.c), under AddressSanitizer + UBSan, whose leak check covers what a failed call leaves behind.
-The drivers must keep no copy of what the layer holds."""
+The drivers must keep no copy of what the layer holds; nor may the sort and scan drivers that use the named stage and
+the copy-out helper of clo_host_pipe.c."""
 import glob
 import os
 import re
@@ -38,3 +39,11 @@ def test_the_drivers_keep_no_copy_of_the_shared_layer():
         for word in ("intern_queue", "error_handler:", "ccl_queue_new(", "ccl_buffer_new(", "calloc(", "clo_stream_guard_enter("):
             assert word not in text, (name, word)
         assert "clo_op_head head;" in text and "clo_stage_close(" in text, name
+    # the upstream-shaped sort and scan drivers: their host-data calls stand on the stage, their pipelines on the drain
+    for name in ("clo_sort_abstract.c", "clo_scan_abstract.c", "clo_sort_satradix.c"):
+        text = open(os.path.join(CSRC, name)).read()
+        assert "pthread_" not in text, name
+        if name != "clo_sort_satradix.c":
+            for word in ("intern_queue", "error_handler:", "ccl_queue_new(", "ccl_buffer_new("):
+                assert word not in text, (name, word)
+            assert "clo_stage_close(" in text, name
