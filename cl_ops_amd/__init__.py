@@ -1,4 +1,4 @@
-"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/selection/top-k primitives and device RNGs behind the cl_ops C API.
+"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/selection/top-k/expansion primitives and device RNGs behind the cl_ops C API.
 
 The product is cl_ops_amd/lib/libcl_ops_hip.so (C-ABI, see include/): host
 drivers in C (cl_ops_amd/csrc) + hand-written HIP kernels for gfx950
@@ -17,6 +17,7 @@ from .merge import Merge, merge_tile  # noqa: F401
 from .search import Search, search_tile, search_lds_keys, search_pivots  # noqa: F401
 from .setop import SetOp, setop_tile  # noqa: F401
 from .select import Select, select_tile  # noqa: F401
+from .expand import Expand, expand_tile, expand_lds_segments, EXPAND_FORMS  # noqa: F401
 from .topk import TopK, topk_tile, topk_sweep_groups, topk_sorted_max, TOPK_WHICH, TOPK_ORDERS  # noqa: F401
 
 __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profiler", "HipEventTimer",
@@ -25,4 +26,5 @@ __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profi
            "Merge", "merge_tile", "Search", "search_tile", "search_lds_keys", "search_pivots",
            "SetOp", "setop_tile", "Select", "select_tile",
            "TopK", "topk_tile", "topk_sweep_groups", "topk_sorted_max", "TOPK_WHICH", "TOPK_ORDERS",
+           "Expand", "expand_tile", "expand_lds_segments", "EXPAND_FORMS",
            "CLO_TYPES", "clo_type", "wait_for_events"]

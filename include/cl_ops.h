@@ -18,6 +18,7 @@
 #include "clo_setop.h"
 #include "clo_select.h"
 #include "clo_topk.h"
+#include "clo_expand.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

@@ -406,6 +406,41 @@ size_t clo_hip_topk_workspace_bytes(size_t numel, int key_size, int value_size);
 int clo_hip_topk(int which, int order, const void* keys_in, const void* values_in, void* keys_out, void* values_out, void* kth_out,
 	size_t numel, size_t k, int key_size, int key_kind, int value_size, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- run-length decode and segment ids (new functionality: CloExpand, include/clo_expand.h) ----
+ * With m = min(numel_in, *num_in) (num_in: a uint64_t of device memory, 8-byte aligned, or NULL: m = numel_in) and the
+ * inclusive ends e_r of the m segments — form CLO_HIP_EXPAND_COUNTS: the running sums, in 64 bits, of the numel_in
+ * counts at counts_or_offsets, those at r >= m adding 0; CLO_HIP_EXPAND_OFFSETS: offsets[r + 1] - offsets[0] of numel_in
+ * + 1 ascending offsets — and total = e_(m-1) (0 for m 0): for every row j < min(total, capacity), with r(j) = the
+ * number of r < m with e_r <= j, values_out[j] = values_in[r(j)] (opaque words of value_size 1, 2, 4 or 8 bytes),
+ * seg_out[j] = r(j) and rank_out[j] = j - e_(r(j)-1), both uint32. Each output may be NULL, not all three; values_in
+ * and values_out come together (value_size is not looked at without them). Rows >= min(total, capacity) are not
+ * written. *num_out = total, unclamped (a uint64_t of device memory, 8-byte aligned). count_size 4 or 8: uint32 or
+ * uint64 counts or offsets.
+ * CLO_HIP_EARGS before anything is enqueued: a form out of range, numel_in or capacity >= 2^32, counts_or_offsets NULL
+ * with numel_in > 0 (offsets: with capacity > 0 too), num_out NULL or misaligned, num_in misaligned, all outputs NULL,
+ * one of values_in / values_out without the other, values with value_size 0, a pointer not aligned to its element, a
+ * missing or misaligned workspace with numel_in > 0. Sizes not built: CLO_HIP_EUNSUPPORTED. A workspace below
+ * clo_hip_expand_workspace_bytes(numel_in, capacity): CLO_HIP_EWORKSPACE. No output may overlap an input, num_in or
+ * another output (not checked here: the driver does). numel_in 0 needs no workspace and still writes *num_out = 0.
+ * Whatever the arrays hold, reads stay inside the inputs, every index gathered by and every seg_out value is below
+ * numel_in, writes stay inside [0, capacity) of the outputs and num_out, and the call completes.
+ * Launches: for the counts form three that write the ends into the workspace (tile sums, one work-group that scans
+ * them, the tiles' write); one thread per tile boundary that finds the tile's first segment by a bounded halving and
+ * writes num_out; one work-group per tile of clo_hip_expand_tile rows, which marks the segment starts in LDS when the
+ * tile has at most clo_hip_expand_lds_segments of them and halves per row in global memory otherwise. No work-group
+ * waits for another and there are no global atomics; asynchronous on `stream`; nothing is allocated and the host never
+ * waits, so the call can be captured into a graph. clo_hip_expand_tile: 0 for value sizes not built (0, none, is
+ * built). clo_hip_expand_workspace_bytes is monotone in both arguments, 0 for (0, 0) and a multiple of
+ * CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_EXPAND_COUNTS 0
+#define CLO_HIP_EXPAND_OFFSETS 1
+size_t clo_hip_expand_tile(int value_size);
+size_t clo_hip_expand_lds_segments(void);
+size_t clo_hip_expand_workspace_bytes(size_t numel_in, size_t capacity);
+int clo_hip_expand(int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* values_in,
+	void* values_out, void* seg_out, void* rank_out, uint64_t* num_out, size_t numel_in, size_t capacity, int value_size,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
