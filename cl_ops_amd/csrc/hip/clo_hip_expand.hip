@@ -6,7 +6,7 @@
 // None of the launches waits for another work-group, none uses a global atomic:
 //   ENDS       the counts form only: the numel_in inclusive ends as uint64 in the workspace, entries at r >= m adding 0.
 //              Three launches (CloSelect's count scan, in 64 bits): the tiles' sums, one work-group that turns them into
-//              exclusive sums EXP_SUMS_TRIP at a time, and the tiles' write. The offsets form is read where it lies.
+//              exclusive sums CLO_OP_SUMS_TRIP at a time, and the tiles' write. The offsets form is read where it lies.
 //   PARTITION  one thread per output tile boundary t * T: first[t] = the number of r < m with e_r <= t * T, 4 bytes per
 //              tile in the workspace; thread 0 writes num_out = total.
 //   EXPAND     one work-group per tile of T rows. first[t] and first[t + 1] are CLAMPED to [0, m] and ordered; the
@@ -41,37 +41,7 @@ constexpr unsigned EXP_TILE = 1u << EXP_TILE_LOG2;               // T: output ro
 constexpr unsigned EXP_PER_THREAD = EXP_TILE / EXP_THREADS;      // 16 consecutive rows of the max scan
 constexpr unsigned EXP_LDS_SEGMENTS = 4 * EXP_TILE;              // L: (segment << 12 | row) must fit a word
 static_assert(((exp_u64) EXP_LDS_SEGMENTS << EXP_TILE_LOG2) < (1ull << 32), "a mark is one word");
-constexpr int EXP_ROW_ELEMS = EXP_THREADS * CLO_OP_VEC;          // 1024 counts: one coalesced stretch
-constexpr int EXP_ENDS_ROWS = 4;
-constexpr unsigned EXP_ENDS_TILE = EXP_ENDS_ROWS * EXP_ROW_ELEMS;   // counts per tile of the ends' scan
-constexpr unsigned EXP_SUMS_ITEMS = 8;
-constexpr unsigned EXP_SUMS_TRIP = EXP_THREADS * EXP_SUMS_ITEMS;    // tile sums per trip of the one-group scan
 constexpr int EXP_HALVE_ITEMS = 4;                               // rows a thread carries through the halving together
-
-// m = min(numel_in, *num_in)
-__device__ __forceinline__ unsigned exp_segments(const exp_u64* __restrict__ num_in, unsigned m_h) {
-	if (!num_in) return m_h;
-	const exp_u64 v = *num_in;
-	return v < m_h ? (unsigned) v : m_h;
-}
-
-// Where the inclusive ends are: the workspace (counts form) or the offsets themselves, rebased. at(r) needs r < m_h.
-template <typename TC, bool OFFSETS>
-struct exp_ends {
-	const TC* off; const exp_u64* ends; exp_u64 base;
-	__device__ __forceinline__ exp_u64 at(unsigned r) const {
-		if constexpr (OFFSETS) return (exp_u64) off[(size_t) r + 1u] - base;
-		else return ends[r];
-	}
-};
-
-template <typename TC, bool OFFSETS>
-__device__ __forceinline__ exp_ends<TC, OFFSETS> exp_ends_make(const TC* __restrict__ src, const exp_u64* __restrict__ ends) {   // m_h > 0
-	exp_ends<TC, OFFSETS> e;
-	e.off = src; e.ends = ends;
-	e.base = OFFSETS ? (exp_u64) src[0] : 0ull;
-	return e;
-}
 
 // THE halving, the only search there is. For each of N rows x[k]: base[k] + how many of the ends [base[k], base[k] +
 // n[k]) are <= x[k], the ends ascending. nmax >= every n[k] sets the number of trips and comes from numel_in; loads are
@@ -96,126 +66,22 @@ __device__ __forceinline__ void exp_halve(const E& e, unsigned (&base)[N], unsig
 	}
 }
 
-// ---- 1. the ends of the counts form ----
-
-// the tile's counts as 64-bit numbers, those at r >= m as 0: row by row, four consecutive ones per lane
-template <typename TC>
-__device__ __forceinline__ void exp_load_counts(const TC* __restrict__ counts, size_t i0, unsigned m_h, unsigned m, bool vec_ok, exp_u64 (&c)[CLO_OP_VEC]) {
-	TC raw[CLO_OP_VEC];
-	clo_op_load4<TC>(counts, i0, m_h, vec_ok, raw);
-	#pragma unroll
-	for (int k = 0; k < CLO_OP_VEC; ++k) c[k] = i0 + k < m ? (exp_u64) raw[k] : 0ull;
-}
+// ---- 1. the ends of the counts form: the three launches of clo_hip_op_device.h ----
 
 template <typename TC>
 __global__ __launch_bounds__(EXP_THREADS)
 void clo_expand_sums_kernel(const TC* __restrict__ counts, const exp_u64* __restrict__ num_in, unsigned m_h, int vec_ok, exp_u64* __restrict__ tsum) {
-	__shared__ exp_u64 s_wave[EXP_WAVES];
-	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const unsigned m = exp_segments(num_in, m_h);
-	const size_t base = (size_t) blockIdx.x * EXP_ENDS_TILE + (size_t) tid * CLO_OP_VEC;
-	exp_u64 sum = 0;
-	#pragma unroll
-	for (int r = 0; r < EXP_ENDS_ROWS; ++r) {
-		exp_u64 c[CLO_OP_VEC];
-		exp_load_counts<TC>(counts, base + (size_t) r * EXP_ROW_ELEMS, m_h, m, vec_ok != 0, c);
-		sum += c[0] + c[1] + c[2] + c[3];
-	}
-	sum = clo_wave_reduce_sum<exp_u64>(sum);
-	if (lane == 0) s_wave[wave] = sum;
-	__syncthreads();
-	if (tid == 0) tsum[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+	clo_op_ends_sums<TC>(counts, num_in, m_h, vec_ok, tsum);
 }
 
-// tsum[0, tiles) -> its exclusive sums in place (modulo 2^64). One work-group; the next trip's sums are requested before
-// this trip's are added.
 __global__ __launch_bounds__(EXP_THREADS)
-void clo_expand_sums_scan_kernel(exp_u64* __restrict__ tsum, unsigned tiles) {
-	__shared__ exp_u64 s_wave[EXP_WAVES];
-	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	exp_u64 carry = 0;
-	exp_u64 v[EXP_SUMS_ITEMS], ahead[EXP_SUMS_ITEMS];
-	#pragma unroll
-	for (unsigned c = 0; c < EXP_SUMS_ITEMS; ++c) {
-		const unsigned i = tid * EXP_SUMS_ITEMS + c;
-		ahead[c] = i < tiles ? tsum[i] : 0ull;
-	}
-	for (unsigned base = 0; base < tiles; base += EXP_SUMS_TRIP) {   // tiles <= 2^20: no wrap
-		exp_u64 sum = 0;
-		#pragma unroll
-		for (unsigned c = 0; c < EXP_SUMS_ITEMS; ++c) {
-			v[c] = ahead[c];
-			sum += v[c];
-			const unsigned i = base + EXP_SUMS_TRIP + tid * EXP_SUMS_ITEMS + c;
-			ahead[c] = i < tiles ? tsum[i] : 0ull;
-		}
-		const exp_u64 incl = clo_wave_scan_inclusive<exp_u64>(sum, lane);
-		if (lane == 63u) s_wave[wave] = incl;
-		__syncthreads();
-		exp_u64 before = 0, total = 0;
-		#pragma unroll
-		for (unsigned w = 0; w < (unsigned) EXP_WAVES; ++w) {
-			const exp_u64 s = s_wave[w];
-			if (w < wave) before += s;
-			total += s;
-		}
-		exp_u64 at = carry + before + incl - sum;
-		#pragma unroll
-		for (unsigned c = 0; c < EXP_SUMS_ITEMS; ++c) {
-			const unsigned i = base + tid * EXP_SUMS_ITEMS + c;
-			if (i < tiles) tsum[i] = at;
-			at += v[c];
-		}
-		carry += total;
-		__syncthreads();   // s_wave is written again
-	}
-}
+void clo_expand_sums_scan_kernel(exp_u64* __restrict__ tsum, unsigned tiles) { clo_op_ends_sums_scan(tsum, tiles); }
 
 template <typename TC>
 __global__ __launch_bounds__(EXP_THREADS)
 void clo_expand_ends_kernel(const TC* __restrict__ counts, const exp_u64* __restrict__ num_in, unsigned m_h, int vec_ok,
 	const exp_u64* __restrict__ tsum, exp_u64* __restrict__ ends) {
-	constexpr int PIECES = EXP_ENDS_ROWS * EXP_WAVES;
-	__shared__ exp_u64 s_piece[PIECES];
-	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const unsigned m = exp_segments(num_in, m_h);
-	const size_t base = (size_t) blockIdx.x * EXP_ENDS_TILE + (size_t) tid * CLO_OP_VEC;
-	exp_u64 c[EXP_ENDS_ROWS][CLO_OP_VEC], before[EXP_ENDS_ROWS];
-	#pragma unroll
-	for (int r = 0; r < EXP_ENDS_ROWS; ++r) {
-		exp_load_counts<TC>(counts, base + (size_t) r * EXP_ROW_ELEMS, m_h, m, vec_ok != 0, c[r]);
-		const exp_u64 t = c[r][0] + c[r][1] + c[r][2] + c[r][3];
-		const exp_u64 incl = clo_wave_scan_inclusive<exp_u64>(t, lane);
-		before[r] = incl - t;
-		if (lane == 63u) s_piece[r * EXP_WAVES + (int) wave] = incl;
-	}
-	__syncthreads();
-	exp_u64 at = tsum[blockIdx.x];
-	#pragma unroll
-	for (int r = 0; r < EXP_ENDS_ROWS; ++r) {
-		#pragma unroll
-		for (int w = 0; w < EXP_WAVES; ++w) {
-			const exp_u64 p = s_piece[r * EXP_WAVES + w];
-			if ((unsigned) w < wave) before[r] += p;
-		}
-		const size_t i0 = base + (size_t) r * EXP_ROW_ELEMS;
-		exp_u64 e[CLO_OP_VEC];
-		exp_u64 run = at + before[r];
-		#pragma unroll
-		for (int k = 0; k < CLO_OP_VEC; ++k) { run += c[r][k]; e[k] = run; }
-		if (i0 + CLO_OP_VEC <= m_h) {   // the workspace is 256-byte aligned and i0 a multiple of 4
-			typedef exp_u64 vec2 __attribute__((ext_vector_type(2)));
-			vec2 a, b;
-			a.x = e[0]; a.y = e[1]; b.x = e[2]; b.y = e[3];
-			*reinterpret_cast<vec2*>(ends + i0) = a;
-			*reinterpret_cast<vec2*>(ends + i0 + 2) = b;
-		} else {
-			#pragma unroll
-			for (int k = 0; k < CLO_OP_VEC; ++k) if (i0 + k < m_h) ends[i0 + k] = e[k];
-		}
-		#pragma unroll
-		for (int w = 0; w < EXP_WAVES; ++w) at += s_piece[r * EXP_WAVES + w];
-	}
+	clo_op_ends_write<TC>(counts, num_in, m_h, vec_ok, tsum, ends);
 }
 
 // ---- 2. partition ----
@@ -225,11 +91,11 @@ void clo_expand_partition_kernel(const TC* __restrict__ src, const exp_u64* __re
 	unsigned tiles, unsigned* __restrict__ first, exp_u64* __restrict__ num_out) {
 	const unsigned t = blockIdx.x * EXP_THREADS + threadIdx.x;
 	if (t > tiles) return;
-	const unsigned m = exp_segments(num_in, m_h);
-	const exp_ends<TC, OFFSETS> e = exp_ends_make<TC, OFFSETS>(src, ends);
+	const unsigned m = clo_op_segments(num_in, m_h);
+	const clo_op_ends<TC, OFFSETS> e = clo_op_ends_make<TC, OFFSETS>(src, ends);
 	unsigned base[1] = { 0u }, n[1] = { m };
 	const exp_u64 x[1] = { (exp_u64) t << EXP_TILE_LOG2 };
-	exp_halve<exp_ends<TC, OFFSETS>, 1>(e, base, n, x, m_h, m_h - 1u);
+	exp_halve<clo_op_ends<TC, OFFSETS>, 1>(e, base, n, x, m_h, m_h - 1u);
 	first[t] = base[0];   // <= m
 	if (t == 0) *num_out = m > 0u ? e.at(m - 1u) : 0ull;
 }
@@ -262,9 +128,9 @@ void clo_expand_kernel(const TC* __restrict__ src, const exp_u64* __restrict__ e
 	__shared__ unsigned s_wave[EXP_WAVES];
 	typedef unsigned vec4 __attribute__((ext_vector_type(4)));
 	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const unsigned m = exp_segments(num_in, m_h);
+	const unsigned m = clo_op_segments(num_in, m_h);
 	if (m == 0u) return;
-	const exp_ends<TC, OFFSETS> e = exp_ends_make<TC, OFFSETS>(src, ends);
+	const clo_op_ends<TC, OFFSETS> e = clo_op_ends_make<TC, OFFSETS>(src, ends);
 	const exp_u64 total = e.at(m - 1u), lim = total < capacity ? total : (exp_u64) capacity;
 	const exp_u64 row0 = (exp_u64) blockIdx.x << EXP_TILE_LOG2;
 	if (row0 >= lim) return;   // the whole work-group
@@ -323,7 +189,7 @@ void clo_expand_kernel(const TC* __restrict__ src, const exp_u64* __restrict__ e
 				base[k] = f0; len[k] = n;
 				x[k] = row0 + tid + (i * EXP_HALVE_ITEMS + (unsigned) k) * EXP_THREADS;
 			}
-			exp_halve<exp_ends<TC, OFFSETS>, EXP_HALVE_ITEMS>(e, base, len, x, m_h, last);
+			exp_halve<clo_op_ends<TC, OFFSETS>, EXP_HALVE_ITEMS>(e, base, len, x, m_h, last);
 			#pragma unroll
 			for (int k = 0; k < EXP_HALVE_ITEMS; ++k) s_row[tid + (i * EXP_HALVE_ITEMS + (unsigned) k) * EXP_THREADS] = base[k];
 		}
@@ -357,11 +223,10 @@ struct exp_args {
 };
 
 inline unsigned exp_tiles(size_t capacity) { return (unsigned) ((capacity + EXP_TILE - 1) / EXP_TILE); }
-inline size_t exp_ends_tiles(size_t numel_in) { return (numel_in + EXP_ENDS_TILE - 1) / EXP_ENDS_TILE; }
 
 template <typename TC>
 int exp_ends_launch(const exp_args& a) {
-	const unsigned tiles = (unsigned) exp_ends_tiles(a.m_h);
+	const unsigned tiles = (unsigned) clo_op_ends_tiles(a.m_h);
 	const int vec_ok = clo_op_vec_ok<TC>(a.src);
 	{
 		clo_timing_scope timing("expand_sums", a.s);
@@ -426,7 +291,7 @@ size_t clo_hip_expand_workspace_bytes(size_t numel_in, size_t capacity) {
 	if (numel_in == 0 && capacity == 0) return 0;
 	// the ends of the counts form, one word per tile boundary, the sums of the ends' scan
 	return clo_op_ws_align(numel_in * sizeof(exp_u64)) + clo_op_ws_align(((size_t) exp_tiles(capacity) + 1) * sizeof(unsigned))
-		+ clo_op_ws_align((exp_ends_tiles(numel_in) + 1) * sizeof(exp_u64));
+		+ clo_op_ws_align((clo_op_ends_tiles(numel_in) + 1) * sizeof(exp_u64));
 }
 
 int clo_hip_expand(int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* values_in,

@@ -19,6 +19,7 @@
 #include "clo_select.h"
 #include "clo_topk.h"
 #include "clo_expand.h"
+#include "clo_segreduce.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

@@ -441,6 +441,39 @@ int clo_hip_expand(int form, const void* counts_or_offsets, int count_size, cons
 	void* values_out, void* seg_out, void* rank_out, uint64_t* num_out, size_t numel_in, size_t capacity, int value_size,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sum, min and max per segment (new functionality: CloSegReduce, include/clo_segreduce.h) ----
+ * m = min(numel_seg, *num_in), the forms (CLO_HIP_SEGREDUCE_COUNTS, CLO_HIP_SEGREDUCE_OFFSETS), the inclusive ends e_r,
+ * count_size and num_out = e_(m-1) unclamped are clo_hip_expand's above. With n = numel rows of values_in and e_(-1) = 0,
+ * for every r < m: aggr_out[r] = op over i in [min(e_(r-1), n), min(e_r, n)) of (sum type) values_in[i], and the
+ * identity where that range is empty (0 for sum, the sum type's largest number for min, its smallest for max). op, the
+ * cast, value_type and sum_type (CloType numbers: int, uint, long or ulong, the sum at least as wide as the value) are
+ * clo_hip_reduce_by_key's. Rows r >= m of aggr_out are not written.
+ * CLO_HIP_EARGS before anything is enqueued: an op or form out of range, numel_seg or numel >= 2^32, counts_or_offsets
+ * NULL with numel_seg > 0 (offsets: always), values_in NULL with numel > 0, aggr_out NULL with numel_seg > 0, num_out
+ * NULL or misaligned, num_in misaligned, a pointer not aligned to its element, a missing or misaligned workspace with
+ * numel_seg > 0. Types and count sizes not built: CLO_HIP_EUNSUPPORTED. A workspace below
+ * clo_hip_segreduce_workspace_bytes(numel_seg, numel): CLO_HIP_EWORKSPACE. Neither output may overlap an input, num_in
+ * or the other output (not checked here: the driver does). numel_seg 0 needs no workspace and writes *num_out = 0 alone.
+ * Whatever the arrays hold, reads stay inside the inputs, writes inside aggr_out[0, numel_seg) and num_out, and the
+ * call completes.
+ * Launches: for the counts form the three of clo_hip_expand that write the ends into the workspace; one thread per tile
+ * boundary of the MERGE of the m clipped ends with the n row indices, which finds its split by a halving and writes
+ * num_out; one work-group per tile of clo_hip_segreduce_tile merge steps (a step closes a segment or takes a row, so
+ * that a tile's work does not depend on how many segments are empty), which writes every segment that closes in it and
+ * leaves the tile's open aggregate in the workspace; one work-group that scans the tiles' open aggregates; one thread
+ * per tile that adds the carry to the tile's first closing segment. values_in is read once. No work-group waits for
+ * another and there are no global atomics; asynchronous on `stream`; nothing is allocated and the host never waits, so
+ * the call can be captured into a graph. clo_hip_segreduce_tile: 0 for sizes not built.
+ * clo_hip_segreduce_workspace_bytes is monotone in both arguments, 0 for (0, 0) and a multiple of
+ * CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_SEGREDUCE_COUNTS 0
+#define CLO_HIP_SEGREDUCE_OFFSETS 1
+size_t clo_hip_segreduce_tile(int value_size, int sum_size);
+size_t clo_hip_segreduce_workspace_bytes(size_t numel_seg, size_t numel);
+int clo_hip_segreduce(int op, int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* values_in,
+	void* aggr_out, uint64_t* num_out, size_t numel_seg, size_t numel, int value_type, int sum_type,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
