@@ -1,5 +1,5 @@
 // clo_hip_op_device.h — what the kernels of the operations that are not upstream share (clo_hip_rbk, sbk, merge,
-// search, setop, select, topk, hist, expand and segreduce .hip). Each piece is here once because its copies were the same
+// search, setop, select, topk, hist, expand, segreduce and segsort .hip). Each piece is here once because its copies were the same
 // text, or differed only by a parameter a copy had fixed; what differs on purpose stays in its file. Everything has
 // internal linkage, and every __global__ function stays in its own file under its own name.
 #ifndef CLO_HIP_OP_DEVICE_H
@@ -333,7 +333,7 @@ __device__ __forceinline__ clo_op_seg_state<TS> clo_op_seg_scan_pieces(const uns
 	return clo_op_seg_wave_exclusive<OP, AGG, TS>(incl, lane);
 }
 
-// ---- the 64-bit segment ends of counts or offsets (expand, segreduce) ----
+// ---- the 64-bit segment ends of counts or offsets (expand, segreduce, segsort) ----
 
 typedef unsigned long long clo_op_u64;
 

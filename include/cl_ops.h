@@ -20,6 +20,7 @@
 #include "clo_topk.h"
 #include "clo_expand.h"
 #include "clo_segreduce.h"
+#include "clo_segsort.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

@@ -474,6 +474,44 @@ int clo_hip_segreduce(int op, int form, const void* counts_or_offsets, int count
 	void* aggr_out, uint64_t* num_out, size_t numel_seg, size_t numel, int value_type, int sum_type,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- a stable sort inside every segment (new functionality: CloSegSort, include/clo_segsort.h) ----
+ * m = min(numel_seg, *num_in), the forms (CLO_HIP_SEGSORT_COUNTS, CLO_HIP_SEGSORT_OFFSETS), the inclusive ends e_r,
+ * count_size and num_out = e_(m-1) unclamped are clo_hip_expand's above. With n = numel rows and e_(-1) = 0, for every
+ * r < m the rows [min(e_(r-1), n), min(e_r, n)) of keys_out hold the same rows of keys_in ascending, equal keys in their
+ * input order; key_type is a CloType number and gives the key's size and its order (unsigned by bits, signed
+ * numerically, half / float / double in IEEE total order); the keys' bits are not changed. values_out[j] is the value
+ * (an opaque word of value_size 4 or 8 bytes) of the row that moved to j; value_size 4 with values_in NULL is the ARG
+ * form: values_out[j] is that row's global index as uint32, and keys_out may then be NULL. Rows >= min(total, n) of the
+ * outputs are not written.
+ * CLO_HIP_EARGS before anything is enqueued: a form out of range, numel_seg or numel >= 2^32, counts_or_offsets NULL
+ * with numel_seg > 0 (offsets: always), keys_in NULL with numel > 0, values with value_size 0, values_out NULL with
+ * value_size > 0, values_in NULL with value_size 8, keys_out NULL outside the arg form, num_out NULL or misaligned,
+ * num_in misaligned, a pointer not aligned to its element, a missing or misaligned workspace with numel_seg > 0. Key
+ * types, value and count sizes not built: CLO_HIP_EUNSUPPORTED. A workspace below
+ * clo_hip_segsort_workspace_bytes(numel_seg, numel, key_size, value_size): CLO_HIP_EWORKSPACE. No output may overlap an
+ * input, num_in or another output (not checked here: the driver does). numel_seg 0 needs no workspace and writes
+ * *num_out = 0 alone. Whatever the arrays hold, reads stay inside the inputs, writes inside [0, numel) of the outputs
+ * and num_out, and the call completes.
+ * The WORKSPACE holds a second copy of the rows (numel keys and numel values; with value_size 4 a third array of numel
+ * keys, which stands in for keys_out when the arg form passes none), a byte per row, rounded up to whole tiles, 32
+ * bytes per tile, and for the counts form 8 bytes per segment: a segment that crosses a tile boundary ping-pongs
+ * between the outputs and that copy.
+ * Launches: for the counts form the three of clo_hip_expand that write the ends; a memset of the row bytes; one thread
+ * per segment that marks the first row of every non-empty segment and writes num_out; one work-group per tile of
+ * clo_hip_segsort_tile rows that sorts them on chip by (segment, key, row) and writes them, which finishes every segment
+ * that lies inside one tile; ceil(log2(tiles)) merge passes, one work-group per output tile, each of which leaves at
+ * once unless a segment of its tile has the middle of a pair of blocks of that pass inside it. No work-group waits for another and there are no global atomics; asynchronous on
+ * `stream`; nothing is allocated and the host never waits, so the call can be captured into a graph.
+ * clo_hip_segsort_tile: T, or 0 for sizes not built. clo_hip_segsort_workspace_bytes is monotone in the two counts, 0
+ * for (0, 0, ., .) and a multiple of CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_SEGSORT_COUNTS 0
+#define CLO_HIP_SEGSORT_OFFSETS 1
+size_t clo_hip_segsort_tile(int key_size, int value_size);
+size_t clo_hip_segsort_workspace_bytes(size_t numel_seg, size_t numel, int key_size, int value_size);
+int clo_hip_segsort(int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* keys_in, const void* values_in,
+	void* keys_out, void* values_out, uint64_t* num_out, size_t numel_seg, size_t numel, int key_type, int value_size,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
