@@ -165,10 +165,13 @@ CCLContext* ccl_context_new_from_menu_full(void* dev_idx_ptr, GError** err) {
 	return ccl_context_new_from_device_index(idx, err);
 }
 
-void ccl_context_ref(CCLContext* ctx) { if (ctx) ++ctx->refcount; }
+/* One context is shared by the objects of every host thread (queues, buffers, sorters, ... each hold a reference), so its
+ * count is the one piece of state two threads change at the same time: atomically. A plain ++ / -- lost updates, the count
+ * reached 0 with references left, and the next ++ wrote into freed memory ("Tests"). */
+void ccl_context_ref(CCLContext* ctx) { if (ctx) __atomic_add_fetch(&ctx->refcount, 1, __ATOMIC_RELAXED); }
 
 void ccl_context_unref(CCLContext* ctx) {
-	if (ctx && --ctx->refcount == 0) free(ctx);
+	if (ctx && __atomic_sub_fetch(&ctx->refcount, 1, __ATOMIC_ACQ_REL) == 0) free(ctx);
 }
 
 void ccl_context_destroy(CCLContext* ctx) { ccl_context_unref(ctx); }

@@ -9,7 +9,10 @@ and select_model equal element-by-element loops written from the headers' defini
 kind, every (key type, which) and (form, order, which), a call whose keys can be loaded as vectors and whose values
 cannot (and the reverse), a cut inside a tie run that takes a whole tile of equal keys, tie runs across a tile edge with
 the cut before and behind the edge, no "sorted" case above the cap and none refused, and topk_model against a plain loop
-over (order key, index) pairs."""
+over (order key, index) pairs. For expand, the segmented reduction and the segmented sort: every structure kind, every
+placement of num_in, of the capacity or the rows and of the offsets' base, a long segment across a tile edge, tiles on both
+sides of expand's switch, wrapped sums and extremes carried in from another tile, every key kind x key size of the
+segmented sort and what the move masks of its cases cover, and the three models against plain loops."""
 import numpy as np
 import pytest
 
@@ -17,12 +20,15 @@ import test_gpu_fuzz as F
 from merge_model import order_key
 from rbk_model import rbk
 from sbk_model import sbk, sbk_loop, identity
+from expand_model import expand
 from search_model import search
+from segreduce_model import segreduce
+from segsort_model import segsort
 from select_model import select
 from setop_model import setop
 from topk_model import topk
 
-FAMILIES = ["rbk", "sbk", "hist", "merge", "search", "setop", "select", "topk"]
+FAMILIES = ["rbk", "sbk", "hist", "merge", "search", "setop", "select", "topk", "expand", "segreduce", "segsort"]
 _ALL = {}
 
 
@@ -41,6 +47,9 @@ def test_the_tables_hold_every_instantiation():
     assert len(F.STRATA["setop"]) == 11 * 5 * 4 == 220
     assert len(F.STRATA["select"]) == 11 * 5 * 2 + 11 == 121
     assert len(F.STRATA["topk"]) == 11 * (5 * 2 + 1) == 121
+    assert len(F.STRATA["expand"]) == 2 * 2 * 5 == 20
+    assert len(F.STRATA["segreduce"]) == 2 * 2 * 12 * 3 == 144
+    assert len(F.STRATA["segsort"]) == 11 * 5 * 2 * 2 == 220
     for f in FAMILIES:
         assert len(set(F.STRATA[f])) == len(F.STRATA[f])
         assert F.SEEDS[f] * F.CASES[f] >= 2 * len(F.STRATA[f])
@@ -78,7 +87,10 @@ def test_sizes_offsets_and_reuse(family):
     assert sum(1 for n, t in sizes if n % t) > len(sizes) // 2               # never only tile multiples
     assert all(n <= (1 << 20) + 6 for n, t in sizes)
     offs = {o for c in cases for o in c["offs"]}
-    assert all(0 <= o <= 31 for o in offs) and len(offs) > 16 and any(o % 2 for o in offs) and max(offs) >= 28
+    if family == "segreduce":                                                # (no array of it has elements below 4 bytes: every multiple of 4)
+        assert offs == set(range(0, 32, 4))
+    else:
+        assert all(0 <= o <= 31 for o in offs) and len(offs) > 16 and any(o % 2 for o in offs) and max(offs) >= 28
     # an object reused: about half of the cases, its constructor arguments unchanged, sizes up and down
     total = lambda c: sum(c[k] for k in two)
     reused = [(a, b) for a, b in zip(cases, cases[1:]) if b["reuse"]]
@@ -481,3 +493,198 @@ def test_topk_cases():
     assert calls >= 200 and at_cap >= 2, (calls, at_cap)
     assert seen >= {"nan payloads", "both zeros", "the winners at the end", "a cut strictly inside a run", "a whole tile of equal keys is taken",
                     "the cut before the tile edge", "the cut behind the tile edge", "all of a run across tiles"}, seen
+
+
+# ---- expand, the segmented reduction and the segmented sort ----
+
+def _segmented_common(family, resolve):
+    """What the three generators promise alike; resolve(c) -> (counts, rows or capacity, num_in, base). Returns the
+    resolved cases."""
+    cases = cases_of(family)
+    assert {c["place"] for c in cases} == set(F.PLACES) and {c["num_in"] for c in cases} == set(F.NUM_INS) and {c["base"] for c in cases} == set(F.BASES)
+    assert {(c["form"], c["ct"]) for c in cases} == {(f, t) for f in ("counts", "offsets") for t in ("uint", "ulong")}
+    assert {c["segments"]["empty"] for c in cases} == set(F.SEG_EMPTY)
+    seen, out = set(), []
+    for c in cases:
+        counts, rows, num_in, base = resolve(c)
+        m, total = counts.size, int(counts.sum())
+        assert counts.dtype == np.int64 and (counts >= 0).all() and total + (m if family == "segreduce" else 0) == c["n"], c
+        assert m >= 1 or (family == "segreduce" and c["n"] == 0)
+        taken = total if num_in is None else int(counts[:num_in].sum())
+        assert {"at": rows == taken, "below": rows < taken or taken == 0, "above": rows > taken}[c["place"]], c
+        assert {"absent": num_in is None, "below": num_in is not None and (num_in < m or m == 0), "at": num_in == m, "above": num_in is not None and num_in > m}[c["num_in"]], c
+        if c["form"] == "offsets":
+            src = F.TSS.source("offsets", c["ct"], counts, base)
+            assert np.array_equal(np.diff(src.astype(np.uint64)), counts.astype(np.uint64)), c       # the base wraps nothing
+            if c["base"] == "top":
+                seen.add("a uint array that ends at 2^32 - 1" if c["ct"] == "uint" and int(src[-1]) == (1 << 32) - 1 else "a ulong base above 2^40")
+        if m > total > 0:
+            seen.add("more segments than rows")
+        z = np.flatnonzero(np.diff(np.concatenate(([1], (counts == 0).astype(np.int8), [1]))))
+        if z.size and (counts == 0).any() and int(np.diff(z).max()) > c["L"] and (counts == 0)[z[np.diff(z).argmax()]]:
+            seen.add("a run of more than L empty segments")
+        if c["segments"]["long"] and int(counts.max()) > 2 * c["tile"]:
+            r = int(counts.argmax())
+            s0 = int(counts[:r].sum()) + (r if family == "segreduce" else 0)                           # its first row, or merge step
+            if s0 // c["tile"] != (s0 + int(counts[r]) - 1) // c["tile"] and s0 + int(counts[r]) <= rows + (r if family == "segreduce" else 0):
+                seen.add("a segment longer than two tiles across a tile edge")
+        if m > 20 and (counts == 0).mean() > 0.4:
+            seen.add("half of the segments empty")
+        if m == 1:
+            seen.add("one segment")
+        out.append((c, counts, rows, num_in, base))
+    assert seen >= {"a uint array that ends at 2^32 - 1", "a ulong base above 2^40", "more segments than rows", "a run of more than L empty segments",
+                    "a segment longer than two tiles across a tile edge", "half of the segments empty", "one segment"}, seen
+    small = [x for x in out if x[0]["n"] <= 5000 and x[1].size <= 20000]
+    assert len(small) >= len(cases) // 6
+    return out, small
+
+
+def expand_loop(form, src, capacity, num_in):
+    """clo_expand.h: segment r owns the rows [e_(r-1), e_r); row j < min(total, capacity) gets r and j - e_(r-1)."""
+    src = [int(x) for x in src]
+    counts = [b - a for a, b in zip(src, src[1:])] if form == "offsets" else src
+    m = len(counts) if num_in is None else min(len(counts), num_in)
+    seg, rank, at = [], [], 0
+    for r in range(m):
+        for k in range(counts[r]):
+            if at + k < capacity:
+                seg.append(r)
+                rank.append(k)
+        at += counts[r]
+    return seg, rank, at
+
+
+def test_expand_cases():
+    resolved, small = _segmented_common("expand", F.expand_inputs)
+    cases = [x[0] for x in resolved]
+    assert {tuple(c["outs"]) for c in cases} == set(F.TE.SUBSETS) and {tuple(c["outs"]) for c in cases if not c["vs"]} == {o for o in F.TE.SUBSETS if not o[0]}
+    seen = set()
+    for c, counts, capacity, num_in, base in resolved:
+        T, L = c["tile"], c["L"]
+        taken = counts if num_in is None else counts[:num_in]
+        ends = np.cumsum(taken)
+        rows = min(int(ends[-1]) if ends.size else 0, capacity)
+        if rows:                                                      # the ends that fall into each tile of output rows
+            per_tile = np.bincount(ends[ends <= rows] // T, minlength=rows // T + 1)
+            seen.update(("a tile with more than L ends",) if per_tile.max() > L else ())
+            seen.update(("a tile with ends, L at the most",) if ((per_tile > 0) & (per_tile <= L)).any() else ())
+    assert seen == {"a tile with more than L ends", "a tile with ends, L at the most"}, seen
+    for c, counts, capacity, num_in, base in small:
+        src = F.TE.source(c["form"], c["ct"], counts, base)
+        seg, rank, total = expand(c["form"], src, capacity, num_in)
+        ls, lr, lt = expand_loop(c["form"], src, capacity, num_in)
+        assert total == lt and seg.tolist() == ls and rank.tolist() == lr, c
+
+
+def segreduce_loop(op, form, src, values, sum_type, num_in):
+    """clo_segreduce.h: the sum modulo 2^bits, the minimum or the maximum of the rows [min(e_(r-1), n), min(e_r, n)) after the C
+    cast to the sum type; the identity for a segment without rows."""
+    dt = np.dtype(F.TSR.NP[sum_type])
+    bits = 8 * dt.itemsize
+    mask = (1 << bits) - 1
+    wrap = lambda x: (x & mask) - (1 << bits) if dt.kind == "i" and (x & mask) >> (bits - 1) else x & mask
+    src = [int(x) for x in src]
+    counts = [b - a for a, b in zip(src, src[1:])] if form == "offsets" else src
+    m = len(counts) if num_in is None else min(len(counts), num_in)
+    v = [wrap(int(x)) for x in values]
+    ident = {"sum": 0, "min": int(np.iinfo(dt).max), "max": int(np.iinfo(dt).min)}[op]
+    out, at = [], 0
+    for r in range(m):
+        rows = v[min(at, len(v)):min(at + counts[r], len(v))]
+        at += counts[r]
+        out.append(ident if not rows else wrap(sum(rows)) if op == "sum" else min(rows) if op == "min" else max(rows))
+    return np.array([x & mask for x in out], dtype="u%d" % dt.itemsize).view(dt), at
+
+
+def test_segreduce_cases():
+    resolved, small = _segmented_common("segreduce", lambda c: (lambda r: (r[0], r[1].size, r[2], r[3]))(F.segreduce_inputs(c)))
+    seen = set()
+    for c, counts, rows, num_in, base in resolved:
+        vals = F.segreduce_inputs(c)[1]
+        assert vals.size == rows and vals.dtype == np.dtype(F.TSR.NP[c["vt"]])
+        T = c["tile"]
+        taken = counts if num_in is None else counts[:num_in]
+        ends = np.minimum(np.cumsum(taken), rows)
+        starts = np.concatenate(([0], ends[:-1]))
+        info = np.iinfo(vals.dtype)
+        for r in np.flatnonzero(ends - starts > 200).tolist():
+            seg = vals[starts[r]:ends[r]]
+            close = (int(ends[r]) + r) // T                                   # the tile of the merge step that closes the segment
+            for ext, name in ((info.min, "min"), (info.max, "max")):
+                at = np.flatnonzero(seg == ext)
+                if at.size == 1 and (int(starts[r]) + int(at[0]) + r) // T != close and not (seg == (info.min + 1 if name == "min" else info.max - 1)).all():
+                    seen.add("the %s of a segment lies in a tile other than the one it closes in" % name)
+                    if c["op"] == name:
+                        seen.add("... and the op is " + name)
+        if c["op"] == "sum" and c["st"] in ("int", "uint") and rows:
+            wide = np.add.reduceat(vals.astype(np.int64), starts[ends > starts]) if (ends > starts).any() else np.zeros(0, np.int64)
+            if (np.abs(wide) >= 1 << 32).any():
+                seen.add("a wrapped 32-bit sum")
+    assert seen >= {"the min of a segment lies in a tile other than the one it closes in", "the max of a segment lies in a tile other than the one it closes in",
+                    "... and the op is min", "... and the op is max", "a wrapped 32-bit sum"}, seen
+    for c, counts, rows, num_in, base in small:
+        vals = F.segreduce_inputs(c)[1]
+        src = F.TSR.source(c["form"], c["ct"], counts, base)
+        aggr, total = segreduce(c["op"], c["form"], src, vals, c["st"], num_in)
+        la, lt = segreduce_loop(c["op"], c["form"], src, vals, c["st"], num_in)
+        assert total == lt and aggr.dtype == la.dtype and np.array_equal(aggr, la), c
+
+
+def test_segsort_cases():
+    import cl_ops_amd as clo
+    import test_segsort_cpu as SC
+    resolved, small = _segmented_common("segsort", lambda c: (lambda r: (r[0], r[1].size, r[2], r[3]))(F.segsort_inputs(c)))
+    cases = [x[0] for x in resolved]
+    kts, sizes = list(F.TSS.KEY_NP), (1, 2, 4, 8)
+    size_of = lambda c: np.dtype(F.TSS.KEY_NP[c["kt"]]).itemsize
+    assert {(c["keys"], size_of(c)) for c in cases} == {(k, s) for k in F.SEGSORT_KEYS for s in sizes}
+    assert {(c["kt"], c["mode"]) for c in cases} == {(kt, m) for kt in kts for m in F.TSS.MODES}
+    assert {(c["form"], c["ct"], size_of(c)) for c in cases} == {(f, t, s) for f in ("counts", "offsets") for t in ("uint", "ulong") for s in sizes}
+    for s in sizes:                                                            # every byte of every key size varies alone somewhere
+        assert {c["digit"] for c in cases if c["keys"] == "one byte varies" and size_of(c) == s} == set(range(s)), s
+    T = clo.segsort_tile(4, 0)
+    seen = set()
+    for c, counts, rows, num_in, base in resolved:
+        assert c["tile"] == T
+        keys = F.segsort_inputs(c)[1]
+        assert keys.size == rows and keys.dtype == np.dtype(F.TSS.KEY_NP[c["kt"]]) and keys.flags.c_contiguous
+        taken = counts if num_in is None else counts[:num_in]
+        ends = np.minimum(np.cumsum(taken), rows)
+        starts = np.concatenate(([0], ends[:-1]))
+        ok = order_key(keys)
+        if c["keys"] in ("sorted", "reversed") and rows > 1:
+            d = np.diff(ok.astype(object)) if rows < 3000 else np.diff(ok.astype(np.float64))
+            assert (d >= 0).all() if c["keys"] == "sorted" else (d <= 0).all(), c
+        if c["keys"] == "all equal" and rows:
+            assert np.unique(ok).size == 1
+        if c["keys"] == "few":
+            assert np.unique(ok).size <= 8
+        if c["keys"] == "one byte varies" and rows > 1000:
+            assert 100 < np.unique(ok).size <= 256 and np.unique(ok >> ok.dtype.type(8 * c["digit"])).size <= 256
+        if c["keys"] == "sorted per segment" and rows:
+            p, _ = segsort(c["form"], F.TSS.source(c["form"], c["ct"], counts, base), keys, num_in)
+            assert np.array_equal(p, np.arange(p.size, dtype=np.uint32)), c   # already the answer
+        if keys.dtype.kind == "f" and rows:
+            b = keys.view("u%d" % keys.itemsize)
+            seen.update(("nan payloads of both signs",) if len(set(b[np.isnan(keys)].tolist())) > 2 and len(set(np.signbit(keys[np.isnan(keys)]).tolist())) == 2 else ())
+            seen.update(("both zeros",) if len(set(b[keys == 0].tolist())) > 1 else ())
+        cross = np.flatnonzero((ends > starts) & (starts // T != (np.maximum(ends, 1) - 1) // T))      # only these have a mask
+        segs = [(int(starts[r]), int(ends[r]), SC.move_mask(int(starts[r]), int(ends[r]), T)) for r in cross.tolist()]
+        for s0, e0, mask in segs:
+            assert mask
+            seen.add("an %s number of moves" % ("odd" if bin(mask).count("1") % 2 else "even"))
+            if "0" in bin(mask)[2:].rstrip("0"):                               # a pass at rest between two moves
+                seen.add("a mask with a gap")
+            if mask.bit_length() - 1 >= 6:
+                seen.add("a highest bit of 6 or more")
+        if SC.opposite_moves_in_one_tile(segs, T):
+            seen.add("a tile whose two boundary segments move in opposite directions")
+    assert seen >= {"nan payloads of both signs", "both zeros", "an odd number of moves", "an even number of moves", "a mask with a gap", "a highest bit of 6 or more",
+                    "a tile whose two boundary segments move in opposite directions"}, seen
+    for c, counts, rows, num_in, base in small:
+        keys = F.segsort_inputs(c)[1]
+        src = F.TSS.source(c["form"], c["ct"], counts, base)
+        p, total = segsort(c["form"], src, keys, num_in)
+        lp, lt = SC._loop(c["form"], src, keys, num_in)
+        assert total == lt and p.tolist() == lp, c

@@ -1,5 +1,5 @@
-"""The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram, CloMerge, CloSearch, CloSetOp, CloSelect and CloTopK on the queue
-production uses (no profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace
+"""The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram, CloMerge, CloSearch, CloSetOp, CloSelect, CloTopK, CloExpand,
+CloSegReduce and CloSegSort on the queue production uses (no profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace
 belongs to one queue at a time"): one object is called six times on two live queues in turn, with no host
 synchronisation between the calls and sizes that make it reuse and outgrow its workspace mid-sequence; then the queue of
 its last call is destroyed and the object is used on a third one, through the host-data and the device form. Last, the
@@ -9,11 +9,14 @@ on the session's profiling queue and of numpy. The results are compared, not the
 import numpy as np
 import pytest
 
+from expand_model import expand
 from hist_model import histogram
 from merge_model import merge, order_key
 from rbk_model import rbk
 from sbk_model import sbk
 from search_model import search
+from segreduce_model import segreduce
+from segsort_model import segsort
 from select_model import select
 from setop_model import setop
 from topk_model import topk
@@ -284,6 +287,106 @@ class _TopKSortedArg(_TopK):
         return ko, vo
 
 
+def _segment_counts(n, seed):
+    """uint counts whose sum is n: lengths geometric with mean 16, a tenth of the segments empty and, where n allows it,
+    one segment of a fifth of the rows: at 2^22 rows it crosses hundreds of tiles of all three operations."""
+    rng = np.random.default_rng(seed)
+    c = rng.geometric(1 / 16, n // 12 + 8)
+    while int(c.sum()) < 2 * n:
+        c = np.concatenate((c, rng.geometric(1 / 16, n // 12 + 8)))
+    c[rng.random(c.size) < 0.1] = 0
+    if n > 100:
+        c[c.size // 7] = n // 5
+    c = c[:int(np.searchsorted(np.cumsum(c), n, "left")) + 1].copy()
+    c[-1] -= int(c.sum()) - n
+    assert int(c.sum()) == n and (c >= 0).all()
+    return c.astype(np.uint32)
+
+
+class _Expand:
+    """n rows from uint counts: the segments' uint values, the segment ids and the ranks. -> (values_out, seg_out,
+    rank_out, the total)."""
+    out_types = (np.uint32, np.uint32, np.uint32, np.uint64)
+
+    def new(self, clo, ctx):
+        return clo.Expand("counts", ctx, "uint", "uint")
+
+    def inputs(self, n, seed):
+        counts = _segment_counts(n, seed)
+        return counts, np.random.default_rng(seed + 1).integers(0, 1 << 32, counts.size, dtype=np.uint64).astype(np.uint32)
+
+    def rows(self, ins):
+        return int(ins[0].sum(dtype=np.uint64))
+
+    def out_counts(self, ins):
+        return self.rows(ins), self.rows(ins), self.rows(ins), 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], None, i[1], o[0], o[1], o[2], o[3], ins[0].size, self.rows(ins))
+
+    def want(self, ins):
+        seg, rank, total = expand("counts", ins[0], self.rows(ins))
+        return ins[1][seg], seg, rank, np.array([total], np.uint64)
+
+    def host(self, obj, q, ins):
+        vo, so, ro, total = obj.with_host_data(ins[0], self.rows(ins), ins[1], seg=True, rank=True, q_exec=q)
+        return vo, so, ro, np.array([total], np.uint64)
+
+
+class _SegReduce(_Expand):
+    """The same counts over n uint values summed in ulong: the ends' scan, the tiles' states, the carry scan and the
+    fix-up talk through the object's workspace. -> (aggr_out, the total)."""
+    out_types = (np.uint64, np.uint64)
+
+    def new(self, clo, ctx):
+        return clo.SegReduce("sum", "counts", ctx, "uint", "ulong", "uint")
+
+    def inputs(self, n, seed):
+        return _segment_counts(n, seed), np.random.default_rng(seed + 1).integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+
+    def out_counts(self, ins):
+        return ins[0].size, 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], None, i[1], o[0], o[1], ins[0].size, ins[1].size)
+
+    def want(self, ins):
+        aggr, total = segreduce("sum", "counts", ins[0], ins[1], "ulong")
+        return aggr, np.array([total], np.uint64)
+
+    def host(self, obj, q, ins):
+        aggr, total = obj.with_host_data(ins[0], ins[1], q_exec=q)
+        return aggr, np.array([total], np.uint64)
+
+
+class _SegSort(_Expand):
+    """The same counts over n uint keys with many ties (5000 values), uint values carried along: the rows ping-pong
+    between the outputs and the copy in the object's workspace, up to eleven merge passes at 2^22 rows.
+    -> (keys_out, values_out, the total)."""
+    out_types = (np.uint32, np.uint32, np.uint64)
+
+    def new(self, clo, ctx):
+        return clo.SegSort("counts", ctx, "uint", 4, "uint")
+
+    def inputs(self, n, seed):
+        rng = np.random.default_rng(seed + 1)
+        return _segment_counts(n, seed), rng.integers(0, 5000, n).astype(np.uint32), rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+
+    def out_counts(self, ins):
+        return ins[1].size, ins[1].size, 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], None, i[1], i[2], o[0], o[1], o[2], ins[0].size, ins[1].size)
+
+    def want(self, ins):
+        p, total = segsort("counts", ins[0], ins[1])
+        return ins[1][p], ins[2][p], np.array([total], np.uint64)
+
+    def host(self, obj, q, ins):
+        ko, vo, total = obj.with_host_data(ins[0], ins[1], ins[2], q_exec=q)
+        return ko, vo, np.array([total], np.uint64)
+
+
 def _same(got, want, what):
     assert len(got) == len(want)
     for k, (g, w) in enumerate(zip(got, want)):
@@ -291,7 +394,8 @@ def _same(got, want, what):
             "%s: output %d differs from the model" % (what, k)
 
 
-@pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge, _Search, _SetOp, _Select, _TopK, _TopKSortedArg], ids=lambda k: k.__name__.strip("_"))
+@pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge, _Search, _SetOp, _Select, _TopK, _TopKSortedArg, _Expand, _SegReduce,
+                                  _SegSort], ids=lambda k: k.__name__.strip("_"))
 def test_object_moves_between_queues(gpu, kind):
     import cl_ops_amd as clo
     ctx, _ = gpu

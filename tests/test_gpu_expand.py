@@ -8,7 +8,8 @@ of the switch between the LDS marks and the per-row search); both forms, both co
 subset of the outputs; num_in and capacity below, at and above; rebased offsets and uint offsets that end at 2^32 - 1;
 chains with the by-key sort, reduce by key and the histogram without a host wait; element-aligned views, two queues, the
 host form, the thin ABI's status codes, a captured graph replayed on other counts; offsets that do not ascend and sums
-that wrap (in bounds, contents not compared); and rows above 2^31 against a closed form."""
+that wrap (in bounds, contents not compared); rows above 2^31 against a closed form; and 2^24 + 5 counts, three trips of
+the shared ends' scan, through all three operations that use it."""
 import itertools
 
 import numpy as np
@@ -68,8 +69,8 @@ def run_expand(dev, form, ct, vs, outs, counts, what, capacity=None, num_in=None
     if capacity is None:
         capacity = total
     what = "%s %s value size %d outs %s, %s" % (form, ct, vs, outs, what)
-    vals = values_for(vs, m_h)
-    ex = obj or clo.Expand(form, ctx, VTYPE[vs], ct)
+    vals = values_for(vs, m_h) if vs else None                            # (value size 0: an object without a value type)
+    ex = obj or clo.Expand(form, ctx, VTYPE.get(vs), ct)
     s_r = Region(rdev, src.nbytes, offs[0], src, 0)
     n_r = Region(rdev, 8, 0, np.array([num_in], np.uint64), 1) if num_in is not None else None
     v_r = Region(rdev, vals.nbytes, offs[1], vals, 1) if outs[0] else None
@@ -162,6 +163,40 @@ def test_sizes_and_count_patterns(dev, TL):
             counts = counts_of(pattern, total, T, case)
             got, _ = run_expand(dev, form, ct, vs, outs, counts, "%s, total %d" % (pattern, total), base=case * 1000)
             assert got == total
+
+
+def ends_scan_counts():
+    """2^24 + 5 counts, all 0 but a 1 at a random 1 in 64 of the positions and at every position within 2 of a multiple of
+    2^20. clo_hip_op_device.h: the one work-group of the shared ends' scan (clo_op_ends_sums_scan) takes CLO_OP_SUMS_TRIP
+    = 2048 tile sums of CLO_OP_ENDS_TILE = 4096 counts per trip, 2^23 counts (no getter): this is three trips, and still
+    two if a trip were doubled."""
+    m = (1 << 24) + 5
+    c = (np.random.default_rng(24).random(m) < 1 / 64).astype(np.int64)
+    for k in range(0, m, 1 << 20):
+        c[max(k - 2, 0):k + 3] = 1
+    return c
+
+
+def test_the_ends_scan_takes_three_trips(dev, TL):
+    """The exclusive sums of the tiles of counts carried from trip to trip, in the counts form of all three operations
+    that share the scan's body (each has __global__ wrappers of its own): seg_out and rank_out of CloExpand with uint and
+    ulong counts and with a num_in just behind the first trip, the sum of ones per segment in CloSegReduce (the counts
+    themselves), and CloSegSort in the keys mode."""
+    from test_gpu_segreduce import run_seg
+    from test_gpu_segsort import run_sort
+    counts = ends_scan_counts()
+    total = int(counts.sum())
+    assert counts.size > 2 << 23 and 200000 < total < 300000
+    for ct in ("uint", "ulong"):
+        got, _ = run_expand(dev, "counts", ct, 4, (False, True, True), counts, "2^24 + 5 counts")
+        assert got == total
+    num_in = (1 << 23) + 3
+    got, _ = run_expand(dev, "counts", "uint", 4, (False, True, True), counts, "num_in just behind 2^23", num_in=num_in, capacity=total)
+    assert got == int(counts[:num_in].sum())
+    got, aggr = run_seg(dev, "sum", "counts", "uint", "uint", "uint", counts, total, "2^24 + 5 counts", vals=np.ones(total, np.uint32))
+    assert got == total and np.array_equal(aggr, counts.astype(np.uint32))
+    got, _, _ = run_sort(dev, "counts", "uint", "ushort", "keys", counts, total, "2^24 + 5 counts", seed=24)
+    assert got == total
 
 
 def test_the_lds_edge(dev, TL):

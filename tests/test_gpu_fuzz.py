@@ -4,7 +4,7 @@ tiles), every radix, element types, in place / out of place, stable pairs — ag
 numpy. Everything goes through the C-ABI of libcl_ops_hip.so.
 
 The second half is the STRATIFIED fuzz of reduce by key, scan by key, histogram, merge, search, the set operations,
-select and top-k: the kernels of those eight are templates over (key size or type x value -> sum conversion, value form x op, mode
+select, top-k, expand, the segmented reduction and the segmented sort: the kernels of those eleven are templates over (key size or type x value -> sum conversion, value form x op, mode
 or path), and draw_cases() walks the list of those instantiations, written out below from the public type rules, so that
 the committed seeds together launch every one; sizes, run structures, bounds, layouts, thresholds, view offsets and the
 reuse of one object over a random sequence of sizes are random per case. draw_cases() and the *_inputs() functions touch
@@ -16,15 +16,19 @@ import pytest
 
 import oracle_lib as O
 import sbk_model
+import test_gpu_expand as TE
 import test_gpu_histogram as TH
 import test_gpu_merge as TM
 import test_gpu_reduce_by_key as TR
 import test_gpu_scan_by_key as TS
 import test_gpu_search as TSE
+import test_gpu_segreduce as TSR
+import test_gpu_segsort as TSS
 import test_gpu_select as TSL
 import test_gpu_setop as TSO
 import test_gpu_topk as TT
 from merge_model import order_key, sort_keys
+from segsort_model import segsort
 
 pytestmark = pytest.mark.gpu
 
@@ -252,7 +256,7 @@ def test_fuzz_sharded_sort_loopback(gpu, seed):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# The stratified fuzz of the eight families
+# The stratified fuzz of the eleven families
 # ----------------------------------------------------------------------------------------------------------------------
 
 _KT_BY_SIZE = {1: ["uchar"], 2: ["ushort"], 4: ["uint", "int", "float"], 8: ["ulong", "double"]}     # reduce / scan by key
@@ -271,8 +275,14 @@ _SELECT_CMP = list(TSL.PREDS[1:])
 # select: (key type, value form, by flags | by comparison), the indices of the set flags without keys_in being a form of
 # the flagged selection alone. topk (include/clo_topk.h): (key type, value form, order), the "sorted" order with its own
 # kernel per (key size, value size) that reads the keys from the workspace where keys_out is not given (arg_only), and
-# the k-th key alone, which stops after the digit sweeps and has no order.
+# the k-th key alone, which stops after the digit sweeps and has no order. expand (include/clo_expand.h): (form, count
+# type, value size, 0 for an object without values); segreduce (include/clo_segreduce.h): (form, count type, (value, sum)
+# pair, op); segsort (include/clo_segsort.h): (key type, value mode, form, count type).
+_COUNT_TYPES = ("uint", "ulong")
 STRATA = {
+    "expand": [(form, ct, vs) for form in TE.FORMS for ct in _COUNT_TYPES for vs in (0, 1, 2, 4, 8)],
+    "segreduce": [(form, ct, pair, op) for form in TSR.FORMS for ct in _COUNT_TYPES for pair in TSR.PAIRS for op in TSR.OPS],
+    "segsort": [(kt, mode, form, ct) for kt in TSS.KEY_NP for mode in TSS.MODES for form in TSS.FORMS for ct in _COUNT_TYPES],
     "rbk": [(ks, kind) for ks in (1, 2, 4, 8) for kind in ["keys_only"] + _BK_KINDS],
     "sbk": [(ks, kind, incl) for ks in (1, 2, 4, 8) for kind in _BK_KINDS for incl in (False, True)],
     "hist": [(ks, sg, cvt, b) for ks in (1, 2, 4, 8) for sg in (0, 1) for cvt in _HIST_CVT for b in _HIST_BINS],
@@ -284,9 +294,12 @@ STRATA = {
 }
 # seeds x cases >= 2 x strata: half the cases of a seed open a new stratum (with a new object), the other half reuse
 # the object of the case before them on a stratum it can run
-SEEDS = {"rbk": 2, "sbk": 3, "hist": 4, "merge": 2, "search": 2, "setop": 8, "select": 4, "topk": 4}
-CASES = {"rbk": 60, "sbk": 76, "hist": 72, "merge": 60, "search": 60, "setop": 60, "select": 62, "topk": 62}
-_SALT = {"rbk": 61, "sbk": 62, "hist": 63, "merge": 64, "search": 65, "setop": 66, "select": 67, "topk": 68}
+SEEDS = {"expand": 2, "segreduce": 4, "segsort": 8, "rbk": 2, "sbk": 3, "hist": 4, "merge": 2, "search": 2, "setop": 8, "select": 4, "topk": 4}
+CASES = {"expand": 60, "segreduce": 72, "segsort": 60, "rbk": 60, "sbk": 76, "hist": 72, "merge": 60, "search": 60, "setop": 60, "select": 62, "topk": 62}
+# expand's object fixes its stratum and there are 20 of them: its seeds open a new object at half of their cases all the
+# same, so that the other half reuses one (every stratum three times over the two seeds)
+_FRESH = {"expand": 30}
+_SALT = {"expand": 69, "segreduce": 70, "segsort": 71, "rbk": 61, "sbk": 62, "hist": 63, "merge": 64, "search": 65, "setop": 66, "select": 67, "topk": 68}
 
 
 def _size(x):
@@ -366,6 +379,10 @@ def _draw_structure(rng, n, tile):
 
 def _object_for(family, rng, stratum):
     """The constructor arguments of a new object that can run the stratum."""
+    if family in ("expand", "segreduce"):
+        return stratum
+    if family == "segsort":
+        return (stratum[0], TSS.VS[stratum[1]], stratum[2], stratum[3])
     if family in ("rbk", "sbk"):
         kt = str(rng.choice(_KT_BY_SIZE[stratum[0]]))
         kind = stratum[1]
@@ -395,6 +412,10 @@ def _object_for(family, rng, stratum):
 
 def compatible(family, obj):
     """The strata an object can run."""
+    if family in ("expand", "segreduce"):
+        return [obj]
+    if family == "segsort":
+        return [(obj[0], m, obj[2], obj[3]) for m in TSS.MODES if TSS.VS[m] == obj[1]]
     if family in ("rbk", "sbk"):
         kt, vt, st, op = obj[:4]
         ks = _size(TR._NP[kt])
@@ -423,6 +444,8 @@ def _draw_call(family, rng, stratum, obj, edge=None, state=None):
     """Everything of one call but the object: plain numbers, strings and lists. state: what select and topk carry from
     case to case (see _draw_select, _draw_topk)."""
     c = {}
+    if family in ("expand", "segreduce", "segsort"):
+        return _draw_segmented(family, rng, stratum, edge, state)
     if family == "search":
         return _draw_search(rng, stratum, edge)
     if family == "setop":
@@ -618,7 +641,7 @@ def draw_cases(family, seed):
     its preds and ops, and topk its directions, in turn over ALL the family's seeds, so the seeds before this one are
     drawn first: still a function of (family, seed) alone.)"""
     state = {}
-    if family in ("select", "topk"):
+    if family in ("select", "topk", "segsort"):
         for earlier in range(seed):
             _draw_seed(family, earlier, state)
     return _draw_seed(family, seed, state)
@@ -627,7 +650,7 @@ def draw_cases(family, seed):
 def _draw_seed(family, seed, state):
     strata = STRATA[family]
     order = np.random.default_rng(_SALT[family]).permutation(len(strata))
-    share = -(-len(strata) // SEEDS[family])
+    share = _FRESH.get(family, -(-len(strata) // SEEDS[family]))
     mine = [strata[int(order[(seed * share + k) % len(strata)])] for k in range(share)]
     total = CASES[family]
     assert 0 <= seed < SEEDS[family] and total >= share
@@ -655,6 +678,12 @@ def _draw_seed(family, seed, state):
 def stratum_of(c):
     """The kernel instantiation a case launches, from the arguments of its call alone."""
     f = c["family"]
+    if f == "expand":
+        return (c["form"], c["ct"], c["vs"])
+    if f == "segreduce":
+        return (c["form"], c["ct"], (c["vt"], c["st"]), c["op"])
+    if f == "segsort":
+        return (c["kt"], c["mode"], c["form"], c["ct"])
     if f in ("rbk", "sbk"):
         ks = _size(TR._NP[c["kt"]])
         if f == "rbk" and not c["want_a"]:
@@ -920,7 +949,180 @@ def topk_inputs(c):
     return keys, int(k)
 
 
+# ---- expand, the segmented reduction and the segmented sort: segments from counts or offsets ----
+
+SEG_EMPTY = [0.0, 0.1, 0.5]                                          # the share of empty segments
+PLACES = ["at", "below", "above"]                                    # the capacity (expand) or the rows, against the total
+NUM_INS = ["absent", "below", "at", "above"]                         # num_in against numel_seg
+BASES = ["zero", "small", "top"]                                     # offsets[0]; top: a uint array ends at 2^32 - 1, a ulong one lies above 2^40
+SEGSORT_KEYS = ["random bits", "specials", "few", "all equal", "sorted", "reversed", "sorted per segment", "one byte varies"]
+
+
+def _draw_segments(rng, n, tile, L, family):
+    """A mixture of geometric stretches (each with a mean of its own from 1 to 50 000), a share of empty segments, one
+    segment longer than two tiles where n allows it, sometimes a run of more than L empty segments (expand's per-row
+    search) and sometimes more segments than rows."""
+    parts = int(rng.integers(1, 5))
+    s = {"seed": int(rng.integers(0, 1 << 30)), "cuts": sorted(int(x) for x in rng.integers(0, n + 1, parts - 1)),
+         "means": [max(1, int(50000.0 ** rng.random())) for _ in range(parts)], "empty": float(rng.choice(SEG_EMPTY)), "long": None,
+         "empty_run": L + 1 + int(rng.integers(0, L)) if rng.random() < 0.2 else 0, "many": bool(rng.random() < 0.15)}
+    if n > 2 * tile + 1:
+        ln = 2 * tile + 1 + int(rng.integers(0, min(tile, n - 2 * tile - 1) + 1))
+        room = n - ln if family != "segreduce" else (n - ln) // 3        # (segreduce's n are merge steps: the rows are cut to fit)
+        s["long"] = (int(rng.integers(0, room + 1)), ln)
+    return s
+
+
+def _draw_segmented(family, rng, stratum, edge, state):
+    import cl_ops_amd as clo
+    L = int(clo.expand_lds_segments())
+    c = {}
+    if family == "expand":
+        form, ct, vs = stratum
+        tile = int(clo.expand_tile(vs))
+        outs = TE.SUBSETS[int(rng.integers(0, len(TE.SUBSETS)))]
+        if not vs:
+            outs = [o for o in TE.SUBSETS if not o[0]][int(rng.integers(0, 3))]
+        sizes = [vs if outs[0] else 0, vs if outs[0] else 0, 4 if outs[1] else 0, 4 if outs[2] else 0]
+        c.update(vs=vs, outs=[bool(o) for o in outs])
+    elif family == "segreduce":
+        form, ct, (vt, st), op = stratum
+        sizes = [_size(TSR.NP[vt]), _size(TSR.NP[st])]
+        tile = int(clo.segreduce_tile(*sizes))
+        c.update(vt=vt, st=st, op=op, plant=[int(rng.integers(0, 50)), int(rng.integers(0, 50)), int(rng.integers(0, 2))])
+    else:
+        kt, mode, form, ct = stratum
+        ks, vs = _size(TSS.KEY_NP[kt]), TSS.VS[mode]
+        tile = int(clo.segsort_tile(ks, vs))
+        sizes = [ks, vs if mode in ("v4", "v8") else 0, ks if mode != "arg without keys_out" else 0, vs]
+        keys = str(rng.choice(SEGSORT_KEYS))
+        digit = None
+        if keys == "one byte varies":                            # the varying byte is dealt: a key size takes its bytes in turn
+            digit = state[("digit", ks)] = (state.get(("digit", ks), -1) + 1) % ks
+        c.update(kt=kt, mode=mode, keys=keys, digit=digit)
+    assert tile > 0
+    n = _draw_n(rng, tile, edge)
+    c.update(form=form, ct=ct, n=n, tile=tile, L=L, segments=_draw_segments(rng, n, tile, L, family), place=str(rng.choice(PLACES)),
+             place_by=int(rng.integers(1, tile)), num_in=str(rng.choice(NUM_INS)), num_in_u=float(rng.random()),
+             base=str(rng.choice(BASES)) if form == "offsets" else "zero", data_seed=int(rng.integers(0, 1 << 30)),
+             offs=[_draw_off(rng, _size(TE.CDT[ct]))] + [_draw_off(rng, x) for x in sizes])
+    return c
+
+
+def segment_counts(c):
+    """The counts of a case: their sum is c["n"] rows; for segreduce the counts and their number together are c["n"] merge
+    steps (the segments are cut off where the steps run out, and a last segment takes what is left)."""
+    s, n = c["segments"], c["n"]
+    rng = np.random.default_rng(s["seed"])
+    bounds = [0] + list(s["cuts"]) + [n]
+    ends = [np.zeros(0, np.int64)]
+    for k, mean in enumerate(s["means"]):
+        if bounds[k + 1] > bounds[k]:
+            ends.append(bounds[k] + np.cumsum(TSS.geometric_fill(rng, bounds[k + 1] - bounds[k], mean)))
+    e = np.unique(np.concatenate(ends))
+    if s["long"]:
+        at, ln = s["long"]
+        e = np.unique(np.concatenate((e[(e <= at) | (e >= at + ln)], [at + ln] + ([at] if at else []))))
+    counts = np.diff(np.concatenate(([0], e))).astype(np.int64)
+    zeros = lambda k: np.zeros(k, np.int64)
+    if s["empty"]:
+        k = int(round(counts.size * s["empty"] / (1.0 - s["empty"])))
+        counts = np.insert(counts, np.sort(rng.integers(0, counts.size + 1, k)), zeros(k))
+    if s["empty_run"]:
+        counts = np.insert(counts, int(rng.integers(0, counts.size + 1)), zeros(s["empty_run"]))
+    if s["many"]:                                                     # more segments than rows
+        k = n + 1 + int(rng.integers(0, n // 4 + 1))
+        counts = np.insert(counts, np.sort(rng.integers(0, counts.size + 1, k)), zeros(k))
+    if c["family"] == "segreduce":
+        steps = np.cumsum(counts + 1)
+        keep = int(np.searchsorted(steps, n, "right"))
+        rest = n - (int(steps[keep - 1]) if keep else 0)
+        counts = np.concatenate((counts[:keep], [rest - 1] if rest else []))
+        assert int(counts.sum()) + counts.size == n
+    else:
+        if not counts.size:
+            counts = zeros(1 + int(rng.integers(0, 3)))              # (at least one segment: numel_seg 0 has tests of its own)
+        assert int(counts.sum()) == n
+    return counts.astype(np.int64)
+
+
+def segmented_args(c, counts):
+    """(the capacity or the rows, num_in, the offsets' base) of a case, resolved on its counts."""
+    m, total = counts.size, int(counts.sum())
+    num_in = {"absent": None, "below": int(c["num_in_u"] * m), "at": m, "above": m + 1 + int(c["num_in_u"] * 1000)}[c["num_in"]]
+    seen = total if num_in is None else int(counts[:num_in].sum())    # the total of the segments the call takes
+    rows = {"at": seen, "below": max(seen - c["place_by"], 0), "above": seen + c["place_by"]}[c["place"]]
+    base = {"zero": 0, "small": 1 + c["data_seed"] % 100000, "top": (1 << 32) - 1 - total if c["ct"] == "uint" else (1 << 40) + c["data_seed"]}[c["base"]]
+    return rows, num_in, base
+
+
+def expand_inputs(c):
+    """(counts, capacity, num_in, base) of an expand case."""
+    counts = segment_counts(c)
+    return (counts,) + segmented_args(c, counts)
+
+
+def segreduce_inputs(c):
+    """(counts, values, num_in, base) of a segreduce case: TSR.values_for's values, and in every segment that crosses
+    a tile edge by more than 100 merge steps on both sides the type's least and greatest value planted, one before and one
+    behind the first edge inside it."""
+    counts = segment_counts(c)
+    rows, num_in, base = segmented_args(c, counts)
+    vals = TSR.values_for(c["vt"], rows, c["data_seed"])
+    info = np.iinfo(vals.dtype)
+    T = c["tile"]
+    idx = np.flatnonzero(counts > 200)
+    start = np.cumsum(counts) - counts
+    for r in idx.tolist():
+        s, ln = int(start[r]), int(counts[r])
+        edge = -(-(s + r + 1) // T) * T                               # the first tile edge behind the segment's first merge step s + r
+        before, behind = s + (edge - (s + r)) - 1 - c["plant"][0], s + (edge - (s + r)) + c["plant"][1]
+        if s + 50 <= before and behind < min(s + ln, rows) - 50:
+            lo, hi = (before, behind) if c["plant"][2] else (behind, before)
+            vals[lo], vals[hi] = info.min, info.max
+    return counts, vals, num_in, base
+
+
+def segsort_inputs(c):
+    """(counts, keys, num_in, base) of a segsort case."""
+    counts = segment_counts(c)
+    n, num_in, base = segmented_args(c, counts)
+    kt, kind = c["kt"], c["keys"]
+    dt = np.dtype(TSS.KEY_NP[kt])
+    ut = np.dtype(TM._U[dt.itemsize])
+    rng = np.random.default_rng(c["data_seed"])
+    if kind == "random bits":
+        keys = _ubits(rng, n, ut).view(dt)
+    elif kind == "specials":                                  # both zeros, NaNs of both signs with payloads, infinities, the types' extremes
+        keys = rng.permutation(TM.keys_of_type(kt, n, c["data_seed"]))
+    elif kind == "few":
+        pool = _ubits(rng, int(rng.integers(2, 9)), ut)
+        keys = pool[rng.integers(0, pool.size, n)].view(dt)
+    elif kind == "all equal":
+        keys = np.repeat(_ubits(rng, 1, ut), n).view(dt)
+    elif kind == "one byte varies":
+        shift = 8 * c["digit"]
+        rest = int(_ubits(rng, 1, ut)[0]) & ~(0xFF << shift)
+        keys = key_of_order((rng.integers(0, 256, n, dtype=np.uint64) << np.uint64(shift) | np.uint64(rest)).astype(ut), dt)
+    else:                                                     # with ties: in the library's order over the whole array, reversed, or per segment
+        pool = _ubits(rng, n // 3 + 1, ut).view(dt)
+        keys = pool[rng.integers(0, pool.size, n)]
+        if kind == "sorted per segment":                      # already the answer
+            keys = np.ascontiguousarray(keys)
+            p, _ = segsort(c["form"], TSS.source(c["form"], c["ct"], counts, base), keys, num_in)
+            keys[:p.size] = keys[p]
+        else:
+            keys = sort_keys(keys)[::-1] if kind == "reversed" else sort_keys(keys)
+    return counts, np.ascontiguousarray(keys), num_in, base
+
+
 def _make_object(clo, ctx, family, obj):
+    if family == "expand":
+        return clo.Expand(obj[0], ctx, TE.VTYPE.get(obj[2]), obj[1])
+    if family == "segreduce":
+        return clo.SegReduce(obj[3], obj[0], ctx, obj[2][0], obj[2][1], obj[1])
+    if family == "segsort":
+        return clo.SegSort(obj[2], ctx, obj[0], obj[1], obj[3])
     if family == "rbk":
         return clo.ReduceByKey(ctx, obj[0], obj[1], obj[2], op=obj[3])
     if family == "sbk":
@@ -972,7 +1174,19 @@ def _run_one(dev, c, handle):
     """The family's own run_case / run_merge: outputs equal the model, rows beyond m untouched, guards intact, inputs
     unchanged, the run count exact."""
     f, what = c["family"], "%s seed %d case %d" % (c["family"], c["seed"], c["case"])
-    if f == "rbk":
+    if f == "expand":
+        counts, capacity, num_in, base = expand_inputs(c)
+        TE.run_expand(dev, c["form"], c["ct"], c["vs"], tuple(c["outs"]), counts, what, capacity=capacity, num_in=num_in, base=base, offs=tuple(c["offs"]),
+                      obj=handle)
+    elif f == "segreduce":
+        counts, vals, num_in, base = segreduce_inputs(c)
+        TSR.run_seg(dev, c["op"], c["form"], c["ct"], c["vt"], c["st"], counts, vals.size, what, num_in=num_in, base=base, offs=tuple(c["offs"]), obj=handle,
+                    vals=vals)
+    elif f == "segsort":
+        counts, keys, num_in, base = segsort_inputs(c)
+        TSS.run_sort(dev, c["form"], c["ct"], c["kt"], c["mode"], counts, keys.size, what + ", %s keys" % c["keys"], num_in=num_in, base=base,
+                     offs=tuple(c["offs"]), obj=handle, seed=c["data_seed"] % 1000, keys=keys)
+    elif f == "rbk":
         keys, values = by_key_inputs(c)
         TR.run_case(dev, c["kt"], c["vt"], c["st"], c["op"], keys, values, what, offs=tuple(c["offs"]), want_k=c["want_k"], want_a=c["want_a"], obj=handle)
     elif f == "sbk":
@@ -1058,3 +1272,18 @@ def test_fuzz_select(gpu, seed):
 @pytest.mark.parametrize("seed", range(SEEDS["topk"]))
 def test_fuzz_topk(gpu, seed):
     _fuzz_family(gpu, "topk", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["expand"]))
+def test_fuzz_expand(gpu, seed):
+    _fuzz_family(gpu, "expand", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["segreduce"]))
+def test_fuzz_segreduce(gpu, seed):
+    _fuzz_family(gpu, "segreduce", seed)
+
+
+@pytest.mark.parametrize("seed", range(SEEDS["segsort"]))
+def test_fuzz_segsort(gpu, seed):
+    _fuzz_family(gpu, "segsort", seed)

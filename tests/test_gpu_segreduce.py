@@ -8,8 +8,8 @@ below, at and above; both forms, both count types, rebased offsets and uint offs
 (value, sum) pair x the three ops on values at the types' extremes; cross-checks against reduce by key on CloExpand's
 segment ids, the round trip through CloExpand and a chain behind reduce by key without a host wait; element-aligned
 views, two queues, the host form, the thin ABI's status codes, a captured graph replayed on other counts and values;
-offsets that do not ascend and sums that wrap (in bounds, contents not compared); and rows above 2^31 against a closed
-form."""
+offsets that do not ascend and sums that wrap (in bounds, contents not compared); rows above 2^31 against a closed
+form; and open aggregates carried across and through whole trips of the one-group carry scan (about 35 M rows)."""
 import numpy as np
 import pytest
 
@@ -55,17 +55,20 @@ def source(form, ct, counts, base=0):
     return (np.concatenate((np.zeros(1, np.uint64), np.cumsum(counts, dtype=np.uint64))) + np.uint64(base)).astype(CDT[ct])
 
 
-def run_seg(dev, op, form, ct, vt, st, counts, n, what, num_in=None, base=0, offs=(0, 0, 0), obj=None, q=None, src=None, compare=True, seed=0):
+def run_seg(dev, op, form, ct, vt, st, counts, n, what, num_in=None, base=0, offs=(0, 0, 0), obj=None, q=None, src=None, compare=True, seed=0,
+            vals=None):
     """One call on views at byte offsets offs = (counts_or_offsets, values_in, aggr_out) with n rows of values; checks
     everything and returns (total, aggr). src: the input as it is (broken preconditions); compare False: the rows'
-    contents are not compared."""
+    contents are not compared; vals: the n values, instead of values_for(vt, n, seed)."""
     clo, ctx, q0 = dev
     q = q or q0
     rdev = (clo, ctx, q)
     if src is None:
         src = source(form, ct, counts, base)
     m_h = src.size - (1 if form == "offsets" else 0)
-    vals = values_for(vt, n, seed)
+    if vals is None:
+        vals = values_for(vt, n, seed)
+    assert vals.dtype == NP[vt] and vals.size == n
     aggr, total = segreduce(op, form, src, vals, st, num_in) if compare else (None, None)
     what = "%s %s %s %s->%s n %d, %s" % (op, form, ct, vt, st, n, what)
     ss = np.dtype(NP[st]).itemsize
@@ -174,6 +177,97 @@ def test_merge_lengths_around_the_tile_edges(dev, T):
             case += 1
             got, _ = run_seg(dev, op, form, ct, vt, st, counts, n, "%d segments + %d rows" % (m, n), seed=case)
             assert got == n
+
+
+# clo_hip_segreduce.hip: SEG_CARRY_TRIP = SEG_THREADS * SEG_CARRY_ITEMS, the tile states the one work-group of the carry
+# scan takes per trip (4096 today; there is no getter). The cases below hold two trips and 108 tiles: three trips, and
+# still a second one if a trip were doubled.
+CARRY_TRIP = 4096
+CARRY_LAYOUTS = ("a segment across each trip edge", "one segment through the whole second trip")
+
+
+def fill_steps(rng, steps, mean=16):
+    """Counts of geometric length that take exactly `steps` merge steps: a segment of c rows takes c + 1, its rows and
+    its end."""
+    if steps <= 0:
+        return np.zeros(0, np.int64)
+    c = rng.geometric(1 / mean, steps // (mean + 1) + 64)
+    while int((c + 1).sum()) < steps:
+        c = np.concatenate((c, rng.geometric(1 / mean, 64)))
+    c = c[:int(np.searchsorted(np.cumsum(c + 1), steps, "left")) + 1].copy()
+    c[-1] -= int((c + 1).sum()) - steps                                   # (0 at the least: an empty segment)
+    assert int((c + 1).sum()) == steps and (c >= 0).all()
+    return c
+
+
+def carry_layout(T, layout):
+    """(counts, [(segment, first row, rows, first step, steps)] of the long segments): 2 * CARRY_TRIP + 108 tiles of merge
+    steps. Positions are in merge steps, rows plus the segment ends before them: segment r with rows [s, e) takes the
+    steps [s + r, e + r]."""
+    E = CARRY_TRIP * T
+    if layout == CARRY_LAYOUTS[0]:
+        spans = ((E - 5 * T // 2, E + 5 * T // 2), (2 * E - T // 2, 2 * E + T // 2))
+    else:
+        spans = ((100 * T + 7, 2 * E + 100 * T - 9),)
+    rng = np.random.default_rng(70 + CARRY_LAYOUTS.index(layout))
+    parts, longs, at, seg, row = [], [], 0, 0, 0
+    for a, b in spans:
+        f = fill_steps(rng, a - at)
+        seg, row = seg + f.size, row + int(f.sum())
+        parts += [f, np.array([b - a - 1])]
+        longs.append((seg, row, b - a - 1, a, b - a))
+        seg, row, at = seg + 1, row + b - a - 1, b
+    parts.append(fill_steps(rng, 2 * E + 108 * T - at))
+    return np.concatenate(parts).astype(np.int64), longs
+
+
+@pytest.fixture(scope="module")
+def carry_cases(T):
+    """The two layouts and one array of values per value type, shared by the cases: in every long segment the type's
+    minimum and maximum are planted within the first T / 2 rows, before the trip edge, so that an aggregate that loses
+    what was carried in is wrong."""
+    layouts = {name: carry_layout(T, name) for name in CARRY_LAYOUTS}
+    rows = max(int(c.sum()) for c, _ in layouts.values())
+    vals = {vt: values_for(vt, rows, 70) for vt in ("int", "uint")}
+    for vt, v in vals.items():
+        info = np.iinfo(NP[vt])
+        for _, longs in layouts.values():
+            for _, row, length, _, _ in longs:
+                assert length > T // 2
+                v[row + 5], v[row + T // 4] = info.min, info.max
+    return layouts, vals
+
+
+@pytest.mark.parametrize("case", range(4))
+@pytest.mark.parametrize("layout", CARRY_LAYOUTS)
+def test_open_aggregates_cross_the_trips_of_the_carry_scan(dev, T, carry_cases, layout, case):
+    """m + n = (2 * 4096 + 108) T merge steps. Layout 1: short segments, one segment over the steps [4096 T - 2.5 T,
+    4096 T + 2.5 T) and one over [8192 T - T / 2, 8192 T + T / 2): an open aggregate is carried from one trip of the carry
+    scan into the next. Layout 2: one segment from step 100 T to step 8292 T: the whole second trip holds no segment end
+    and the carried state passes through it unchanged."""
+    op, vt, st = (("sum", "int", "long"), ("sum", "uint", "uint"), ("min", "int", "int"), ("max", "uint", "uint"))[case]
+    layouts, vals = carry_cases
+    counts, longs = layouts[layout]
+    m, n = counts.size, int(counts.sum())
+    E = CARRY_TRIP * T
+    assert m + n == 2 * E + 108 * T
+    if layout == CARRY_LAYOUTS[0]:                                        # the segments lie where the docstring says
+        assert [(first, steps) for _, _, _, first, steps in longs] == [(E - 5 * T // 2, 5 * T), (2 * E - T // 2, T)]
+    else:
+        (_, _, _, first, steps), = longs
+        assert first < E and first + steps > 2 * E + T
+    for seg, row, length, first, steps in longs:                          # ... in merge steps: rows plus ends before
+        assert counts[seg] == length and int(counts[:seg].sum()) == row and row + seg == first and length + 1 == steps
+    k = case + CARRY_LAYOUTS.index(layout)
+    got, aggr = run_seg(dev, op, FORMS[k % 2], ("uint", "ulong")[k // 2 % 2], vt, st, counts, n, layout, base=7 * k, vals=vals[vt][:n])
+    assert got == n
+    info = np.iinfo(NP[vt])
+    for seg, row, length, _, _ in longs:
+        if op != "sum":
+            assert aggr[seg] == (info.min if op == "min" else info.max), (layout, op, seg)
+    if vt == "uint" and op == "sum":                                      # the sums wrap
+        wide = np.add.reduceat(vals["uint"][:n].astype(np.uint64), np.cumsum(counts)[:-1][counts[1:] > 0][:1000])
+        assert (wide >= 1 << 32).any()
 
 
 def test_empty_segments(dev, T):

@@ -2,7 +2,8 @@
 context: the threading contract of the reference (no locks, no mutable globals: an object is not re-entrant, distinct
 objects are independent — SURVEY §8b "Threading"). ctypes drops the GIL during a call, so the C drivers, their workspace
 caches and the run-time compiler really do run side by side here. Every result is checked bit for bit against numpy.
-The by-key sort, reduce by key, scan by key, histogram, merge, search, the set operations, select and top-k run the same way
+The by-key sort, reduce by key, scan by key, histogram, merge, search, the set operations, select, top-k, expand, the
+segmented reduction and the segmented sort run the same way
 (the adapters of test_gpu_by_key_queues.py: inputs, the device call, the host-data call and the model of each), and
 give their device memory back like the sorters and scanners."""
 import threading
@@ -179,6 +180,26 @@ def test_topk_objects_on_distinct_threads(clo):
     ctx.close()
 
 
+def test_segmented_objects_on_distinct_threads(clo):
+    """Five threads in one process: an expand, a segmented reduction and a segmented sort (the ends' scan in each one's
+    workspace; the sort's second copy of the rows) next to one satradix sorter and one scanner."""
+    import test_gpu_by_key_queues as K
+    ctx = clo.Context(0)
+    errors = []
+    workers = [threading.Thread(target=_by_key_worker, args=(clo, ctx, kind, 80 + i, 16, 21, errors))
+               for i, kind in enumerate((K._Expand, K._SegReduce, K._SegSort))]
+    workers += [threading.Thread(target=_sort_worker, args=(clo, ctx, "satradix", "uint", 86, 16, 21, errors)),
+                threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "ulong", 87, 16, 21, errors))]
+    assert len(workers) == 5
+    for w in workers:
+        w.start()
+    for w in workers:
+        w.join(timeout=600)
+    assert not any(w.is_alive() for w in workers), "a worker is stuck"
+    assert errors == []
+    ctx.close()
+
+
 def test_sorters_built_by_the_runtime_compiler_side_by_side(clo):
     """Two threads construct sorters through hiprtc at once (different key expressions) and sort with them."""
     ctx = clo.Context(0)
@@ -322,6 +343,13 @@ def test_topk_objects_give_their_device_memory_back(clo):
     """And for the two top-k objects of test_gpu_by_key_queues.py: a cached workspace each."""
     import test_gpu_by_key_queues as K
     _give_back(clo, (K._TopK, K._TopKSortedArg))
+
+
+def test_segmented_objects_give_their_device_memory_back(clo):
+    """And for an expand, a segmented reduction and a segmented sort: a cached workspace each, the sort's with a second
+    copy of the rows."""
+    import test_gpu_by_key_queues as K
+    _give_back(clo, (K._Expand, K._SegReduce, K._SegSort))
 
 
 def _give_back(clo, kinds):

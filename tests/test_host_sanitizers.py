@@ -4,7 +4,9 @@ implementation of the thin C-ABI, test infrastructure only — and driven by tes
 the pipelined clo_sort_with_host_data / clo_scan_with_host_data (helper threads), and the sharded sort of
 include/clo_shard.h with 1, 2, 4 and 8 ranks as threads over an in-memory transport (slices, pieces, growth,
 ranks failing together). Once with AddressSanitizer + UBSan, once with ThreadSanitizer; a run must end with
-exit code 0 and without a single sanitizer report."""
+exit code 0 and without a single sanitizer report. And the one piece of state that objects of different host threads
+share, the context's reference count, taken and dropped by eight threads at once under ThreadSanitizer
+(tests/ccl_host/context_refs_test.c)."""
 import glob
 import os
 import subprocess
@@ -44,6 +46,20 @@ def test_host_paths_under_sanitizers(tmp_path, name, flags, needles):
     assert r.returncode == 0 and "shard fuzz ok" in r.stdout, out[-4000:]
     for n in needles:
         assert n not in out, out[-4000:]
+
+
+def test_context_references_from_eight_threads(tmp_path):
+    """Queues, buffers and operation objects each hold a reference to their context, and test_gpu_threads.py uses one
+    context from up to seven threads: the count has to be atomic. (With a plain ++ / -- it lost updates, reached 0 with
+    references left, and the next ++ wrote into freed memory: glibc's "unsorted double linked list corrupted".)"""
+    exe = str(tmp_path / "context_refs")
+    srcs = [os.path.join(ROOT, "cl_ops_amd", "csrc", "clo_ccl.c"), os.path.join(ROOT, "cl_ops_amd", "csrc", "clo_common.c"),
+            os.path.join(ROOT, "tests", "hoststub", "clo_hip_stub.c"), os.path.join(ROOT, "tests", "ccl_host", "context_refs_test.c")]
+    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-D_GNU_SOURCE", "-fno-omit-frame-pointer", "-w", "-fsanitize=thread",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cl_ops_amd", "csrc"), *srcs, "-lpthread", "-lm", "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0"))
+    out = r.stdout + r.stderr
+    assert r.returncode == 0 and "context refs ok" in r.stdout and "ThreadSanitizer" not in out, out[-4000:]
 
 
 def test_the_stub_is_not_in_the_product():

@@ -4,7 +4,10 @@ offline context before anything touches a device (err == NULL included) and leav
 without a device, and the C driver runs over the host stubs of the thin C-ABI (tests/hoststub/*stub*.c, among them
 clo_hip_segsort_stub.c) under AddressSanitizer + UBSan, driven by the stand-alone program
 tests/segsort_host/segsort_host_test.c. The reference model the GPU tests compare against (segsort_model.py) is checked
-here against a plain Python loop that sorts every clipped segment with Python's stable sort."""
+here against a plain Python loop that sorts every clipped segment with Python's stable sort. The move rule of the merge
+passes is restated here from its prose, and the cases of tests/test_gpu_segsort.py above ten tiles
+are shown to have the masks they claim; the table of thin-ABI argument tuples of that file runs through the host stub
+built as a shared library, so that the stub and the device code answer the same tuples alike."""
 import ctypes as C
 import glob
 import os
@@ -320,3 +323,139 @@ def test_the_model_against_a_plain_loop():
                             assert (p.tolist(), t) == (_loop(form, src, keys, num_in)[0], _loop(form, src, keys, num_in)[1]), what
     p, t = segsort("counts", np.array([1 << 63, 1 << 63, 5], np.uint64), np.arange(4, dtype=np.uint32))   # ends modulo 2^64
     assert t == 5                                                             # (the ends do not ascend: the rows' contents are unspecified)
+
+
+# ---- the move rule of DESIGN.md section 22, restated from its prose, and what the GPU cases promise about it ----
+
+def move_mask(s, e, T):
+    """Bit p: pass p moves the segment [s, e). Pass p works on blocks of W = T * 2^p rows; with a the block of the
+    segment's first row and b of its last, the segment moves iff there is an odd k with a < k <= b (the middle of a pair
+    of blocks strictly inside it). From the pass at which a == b on, nothing moves."""
+    mask, p = 0, 0
+    while s < e:
+        W = T << p
+        a, b = s // W, (e - 1) // W
+        if a == b:
+            break
+        odd = a + 1 if (a + 1) % 2 else a + 2                                 # the smallest odd k above a
+        if odd <= b:
+            mask |= 1 << p
+        p += 1
+    return mask
+
+
+def segment_masks(counts, n, T):
+    """[(s, e, mask)] of the non-empty clipped segments."""
+    ends = np.minimum(np.cumsum(np.asarray(counts, np.int64)), n)
+    starts = np.concatenate(([0], ends[:-1]))
+    return [(int(s), int(e), move_mask(int(s), int(e), T)) for s, e in zip(starts, ends) if e > s]
+
+
+def opposite_moves_in_one_tile(segs, T):
+    """The tiles whose first row's and last row's segments differ, both move in some pass p, and have moves of different
+    parity left at p: one is read from the workspace and the other from the outputs by the same work-group."""
+    found = []
+    by_tile = {}
+    for s, e, m in segs:
+        if m:
+            by_tile.setdefault(s // T, []).append((s, e, m))                  # the tile of its first row: it is B there
+            by_tile.setdefault((e - 1) // T, []).append((s, e, m))            # ... and A in the tile of its last row
+    for t, both in by_tile.items():
+        A = [g for g in both if g[0] < t * T]                                 # starts before the tile
+        B = [g for g in both if g[1] > (t + 1) * T]                           # ends behind it
+        for a in A:
+            for b in B:
+                if a is b:
+                    continue
+                for p in range(32):
+                    if (a[2] >> p) & 1 and (b[2] >> p) & 1 and (bin(a[2] >> p).count("1") + bin(b[2] >> p).count("1")) % 2:
+                        found.append((t, p))
+    return found
+
+
+def test_the_move_masks_the_gpu_cases_pin():
+    """What tests/test_gpu_segsort.py's cases above ten tiles claim to reach, shown on the CPU: the pinned masks, a tile
+    whose two boundary segments move in opposite directions in one pass, and every pass 0 .. 8 as the highest bit of
+    some mask."""
+    import test_gpu_segsort as G
+    T = clo.segsort_tile(4, 0)
+    assert move_mask(0, T, T) == 0 and move_mask(T - 1, T + 1, T) == 1 and move_mask(0, 3 * T, T) == 0b11
+    assert move_mask(3 * T + T // 2, 4 * T + T // 2, T) == 0b100 and move_mask(0, 8 * T + 1, T) == 0b1111   # section 22's own examples
+    highest = set()
+    n = G.PINNED_TILES * T
+    segs = segment_masks(G.pinned_counts(T, G.PINNED_TILES, G.PINNED), n, T)
+    long = [g for g in segs if g[1] - g[0] > 200]
+    assert [(2 * s // T, 2 * e // T) for s, e, _ in long] == list(G.PINNED)
+    assert tuple(m for _, _, m in long) == G.PINNED_MASKS == (0b101, 0b1001, 0b10011, 0b100001, 0b1000000)
+    highest |= {m.bit_length() - 1 for _, _, m in segs if m}
+    for k in G.SINGLE_BIT:
+        segs = segment_masks(G.pinned_counts(T, k + 2, ((2 * k - 1, 2 * k + 1),), seed=k), (k + 2) * T, T)
+        assert [m for s, e, m in segs if e - s > 200] == [k]
+        highest |= {m.bit_length() - 1 for _, _, m in segs if m}
+    for size in G.big_sizes(T):
+        m = move_mask(0, size, T)
+        assert m == (1 << (m.bit_length())) - 1                               # a segment from row 0 moves at every pass up to its last
+        highest.add(m.bit_length() - 1)
+    assert {3, 4, 5} <= {move_mask(0, size, T).bit_length() - 1 for size in G.big_sizes(T)}
+    counts = G.end_to_end_counts(T)
+    assert int(counts.sum()) == G.END_TO_END_TILES * T and counts.min() >= 1 and counts[:-1].min() >= T // 2 and counts.max() <= 40 * T
+    segs = segment_masks(counts, G.END_TO_END_TILES * T, T)
+    assert opposite_moves_in_one_tile(segs, T), "no tile of the end-to-end case has A and B with different parities in a pass where both move"
+    assert max(bin(m).count("1") for _, _, m in segs) >= 4 and any((e - s) > 32 * T for s, e, _ in segs)   # a merge with a part above 4 T
+    highest |= {m.bit_length() - 1 for _, _, m in segs if m}
+    assert set(range(9)) <= highest, sorted(highest)
+
+
+def _aligned(nbytes, fill=0xA5, align=256):
+    """(owner, address, view): nbytes of host memory at a multiple of `align`, filled."""
+    raw = np.full(nbytes + align, fill, np.uint8)
+    at = -raw.ctypes.data % align
+    return raw, raw.ctypes.data + at, raw[at:at + nbytes]
+
+
+def test_the_host_stub_answers_the_thin_abi_table_as_the_device_code_does(tmp_path):
+    """tests/hoststub/clo_hip_segsort_stub.c restates the rules of clo_hip_segsort; the GPU test runs the table of
+    test_gpu_segsort.ThinABI through the device code, this runs the same table through the stub: the same status for
+    every refused tuple (but the workspace's alignment, which the stub cannot check), nothing written, and the model's
+    rows for every accepted one."""
+    import test_gpu_segsort as G
+    so = str(tmp_path / "libsegsort_stub.so")
+    subprocess.check_call(["gcc", "-O1", "-std=c11", "-shared", "-fPIC", "-w", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "hoststub", "clo_hip_segsort_stub.c"), "-o", so])
+    stub = C.CDLL(so)
+    vp, ci, sz = C.c_void_p, C.c_int, C.c_size_t
+    stub.clo_hip_segsort.restype = ci
+    stub.clo_hip_segsort.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, sz, vp]
+    stub.clo_hip_segsort_workspace_bytes.restype = sz
+    stub.clo_hip_segsort_workspace_bytes.argtypes = [sz, sz, ci, ci]
+    lib = clo.api.lib
+    T = clo.segsort_tile(4, 0)
+    abi = G.ThinABI(T, clo.CLO_TYPES, lib.clo_hip_segsort_workspace_bytes)
+    for a, b, ks, vs in ((abi.m_h, abi.n, 4, 4), (abi.m_h + 1, abi.n + 1, 8, 8), (0, 0, 4, 4), (5, 0, 1, 0), (0, 7, 2, 4), (abi.m_h, abi.n, 3, 4)):
+        assert stub.clo_hip_segsort_workspace_bytes(a, b, ks, vs) == lib.clo_hip_segsort_workspace_bytes(a, b, ks, vs), (a, b, ks, vs)
+    held = {}
+    for name, data in (("cn", abi.counts), ("ki", abi.keys), ("vi", abi.vals), ("ni", abi.num_in)):
+        held[name] = _aligned(data.nbytes)
+        held[name][2][:] = data.view(np.uint8)
+    for name, nbytes in (("ko", abi.out_bytes), ("vo", abi.out_bytes), ("num", 16), ("ws", abi.big)):
+        held[name] = _aligned(nbytes)
+    P = {k: v[1] for k, v in held.items()}
+    call = lambda kw: stub.clo_hip_segsort(*[kw[k] for k in G.ThinABI.ORDER], None)
+    checked = 0
+    for what, kw, status, on_stub in abi.refusals(P):
+        if on_stub:
+            assert call(kw) == status, what
+            checked += 1
+    assert checked >= 40
+    for name in ("ko", "vo", "num"):
+        assert (held[name][2] == 0xA5).all(), "a refused call wrote " + name
+    for what, kw, spec in abi.accepted(P):
+        assert call(kw) == 0, what
+        want_k, want_v, total = abi.want(spec, kw["form"]) if spec[4] else (None, None, 0)
+        assert int(held["num"][2][:8].view(np.uint64)[0]) == total, what
+        for name, want in (("ko", want_k), ("vo", want_v)):
+            if kw[name] is not None and want is not None:
+                at = 4 * spec[0]
+                assert np.array_equal(held[name][2][at:at + want.nbytes], want.view(np.uint8)), (what, name)
+    for name, data in (("cn", abi.counts), ("ki", abi.keys), ("vi", abi.vals), ("ni", abi.num_in)):
+        assert np.array_equal(held[name][2], data.view(np.uint8)), name
