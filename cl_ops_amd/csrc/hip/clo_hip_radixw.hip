@@ -29,6 +29,14 @@ template <typename E, bool BIG> struct rw_shape {
 	static constexpr int TILE = pair_shape<E, BIG>::TILE;
 	static constexpr int THREADS = pair_shape<E, BIG>::THREADS;
 	static constexpr int ITEMS = TILE / THREADS;
+	// The histograms' whole-tile loads are marked non-temporal (`global_load_dwordx4 ... nt`) on this shape: the bytes are
+	// read once, and lanes read adjacent vectors, so nothing is lost with the L1 the mark also bypasses. Decided per shape,
+	// interleaved against the build without it (profiles/ab_stream_loads.txt, docs/lab_notebook.md): 4-byte elements on big
+	// tiles — histograms 0.110 -> 0.088 ms per pass of 2^28 keys, the pass kernel that follows gives 0.008 back, the sort
+	// 2.36 -> 2.31 ms; 2^26 0.662 -> 0.645. 8-byte elements on big tiles: no difference. The 512-thread shape (arrays that
+	// sit in the last-level cache): 2^22 keys 0.0916 -> 0.0932 ms, slower. The same mark on the pass kernel's own loads —
+	// a thread's 64 consecutive bytes, four instructions to a cache line — lost a quarter of its speed (0.47 -> 0.58 ms).
+	static constexpr bool STREAM = BIG && sizeof(E) == 4;
 };
 
 // The histogram kernels also zero the hand-off words of the counter scan that follows them on the stream
@@ -94,6 +102,7 @@ void clo_radixw_tilehist_kernel(const L* __restrict__ in, size_t n, unsigned shi
 	constexpr int VB = ITEMS * (int) sizeof(L) >= 16 ? 16 : ITEMS * (int) sizeof(L);   // bytes per vector load
 	constexpr int VECS = ITEMS * (int) sizeof(L) / VB;
 	constexpr int PER = VB / (int) sizeof(L);
+	constexpr bool STREAM = rw_shape<E, BIG>::STREAM;
 	// 32 copies of every counter, copy = lane mod 32, bin-major: the 32 lanes an LDS
 	// instruction serves together hit 32 different banks and never one address (an
 	// LDS add holds its bank for many cycles; one copy per wave, lanes colliding on
@@ -121,7 +130,7 @@ void clo_radixw_tilehist_kernel(const L* __restrict__ in, size_t n, unsigned shi
 		// kernel reads them, are 64 different cache-line halves per instruction): 2^28 uint32 sorts -0.012 ms, round 5.
 		const vecE* p = reinterpret_cast<const vecE*>(in + base) + ptid;
 		#pragma unroll
-		for (int k = 0; k < VECS; ++k) v[k] = p[k * PART];
+		for (int k = 0; k < VECS; ++k) v[k] = STREAM ? __builtin_nontemporal_load(p + k * PART) : p[k * PART];
 	}
 	{   // (16-byte stores: a quarter of the LDS instructions of a dword loop)
 		typedef unsigned vec4u __attribute__((ext_vector_type(4)));
@@ -183,6 +192,7 @@ void clo_radixw_tilehist_bytes_kernel(const unsigned char* __restrict__ dig, siz
 	constexpr int PART = THREADS / TPW;   // threads of one tile
 	constexpr int TILE = PART * ITEMS;
 	constexpr int COPIES = 32;
+	constexpr bool STREAM = ITEMS == 32;   // the stream of 4-byte elements (rw_shape<E, true>::STREAM: measured per shape)
 	static_assert(PART % 64 == 0 && PART * TPW == THREADS, "whole waves per tile");
 	__shared__ __attribute__((aligned(16))) unsigned s_cnt[TPW * R * COPIES];
 	const unsigned tid = threadIdx.x, lane = tid & 63u;
@@ -213,7 +223,7 @@ void clo_radixw_tilehist_bytes_kernel(const unsigned char* __restrict__ dig, siz
 		const q4* p = reinterpret_cast<const q4*>(dig + base) + ptid;
 		#pragma unroll
 		for (int k = 0; k < ITEMS / 16; ++k) {
-			const q4 x = p[k * PART];
+			const q4 x = STREAM ? __builtin_nontemporal_load(p + k * PART) : p[k * PART];
 			#pragma unroll
 			for (int q = 0; q < 4; ++q) v[k * 4 + q] = x[q];
 		}
