@@ -33,7 +33,7 @@ from segsort_model import segsort
 pytestmark = pytest.mark.gpu
 
 # boundaries of the radix paths, in elements: one launch <= 16384 (8192 of 8 bytes), sweeps up to
-# 1024 tiles of 8192 (4096), big tiles from 64 MiB (8-byte) / 256 MiB (4-byte)
+# 1024 tiles of 8192 (4096), big tiles from 32 MiB (8-byte) / 256 MiB (4-byte)
 EDGES_4 = [1, 2, 17, 4095, 4096, 4097, 8192, 16384, 16385, 32768 + 1, (1 << 20) - 1, (1 << 23), (1 << 23) + 8193, (1 << 24) + 5]
 EDGES_8 = [1, 3, 4096, 8192, 8193, 16385, (1 << 19) + 77, (1 << 22), (1 << 22) + 4097, (1 << 23) - 1, (1 << 23) + 16385]
 

@@ -624,7 +624,7 @@ def test_radix_sort_fed_with_first_digits(gpu, kind, logn, shift, bits):
     key = (a >> dt(shift)) & dt((1 << bits) - 1 if bits < 64 else np.iinfo(dt).max)
     lib.clo_hip_env_refresh()        # (the switches are read when an object is made: none has been, in this test, since an earlier one changed them)
     takes = lib.clo_hip_radix_takes_first_digits(n, es, 0, 4)
-    assert takes == (1 if n * es >= ((64 if es == 8 else 256) << 20) else 0)
+    assert takes == (1 if n * es >= ((32 if es == 8 else 256) << 20) else 0)   # (clo_big_tile_bytes)
     wsb = lib.clo_hip_radix_workspace_bytes(n, es, bits, 4)
     src, dst, tmp, ws = clo.Buffer(ctx, n * es), clo.Buffer(ctx, n * es), clo.Buffer(ctx, n * es), clo.Buffer(ctx, wsb)
     src.write(q, a)
