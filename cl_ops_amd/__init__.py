@@ -1,4 +1,4 @@
-"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/selection/top-k/expansion/segmented-reduction/segmented-sort primitives and device RNGs behind the cl_ops C API.
+"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/selection/top-k/expansion/segmented-reduction/segmented-sort/segmented-scan primitives and device RNGs behind the cl_ops C API.
 
 The product is cl_ops_amd/lib/libcl_ops_hip.so (C-ABI, see include/): host
 drivers in C (cl_ops_amd/csrc) + hand-written HIP kernels for gfx950
@@ -20,6 +20,7 @@ from .select import Select, select_tile  # noqa: F401
 from .expand import Expand, expand_tile, expand_lds_segments, EXPAND_FORMS  # noqa: F401
 from .segreduce import SegReduce, segreduce_tile, SEGREDUCE_OPS, SEGREDUCE_FORMS  # noqa: F401
 from .segsort import SegSort, segsort_tile, SEGSORT_FORMS  # noqa: F401
+from .segscan import SegScan, segscan_tile, SEGSCAN_OPS, SEGSCAN_FORMS  # noqa: F401
 from .topk import TopK, topk_tile, topk_sweep_groups, topk_sorted_max, TOPK_WHICH, TOPK_ORDERS  # noqa: F401
 
 __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profiler", "HipEventTimer",
@@ -31,4 +32,5 @@ __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profi
            "Expand", "expand_tile", "expand_lds_segments", "EXPAND_FORMS",
            "SegReduce", "segreduce_tile", "SEGREDUCE_OPS", "SEGREDUCE_FORMS",
            "SegSort", "segsort_tile", "SEGSORT_FORMS",
+           "SegScan", "segscan_tile", "SEGSCAN_OPS", "SEGSCAN_FORMS",
            "CLO_TYPES", "clo_type", "wait_for_events"]

@@ -21,6 +21,7 @@
 #include "clo_expand.h"
 #include "clo_segreduce.h"
 #include "clo_segsort.h"
+#include "clo_segscan.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

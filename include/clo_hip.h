@@ -512,6 +512,39 @@ int clo_hip_segsort(int form, const void* counts_or_offsets, int count_size, con
 	void* keys_out, void* values_out, uint64_t* num_out, size_t numel_seg, size_t numel, int key_type, int value_size,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- running sum, min and max within segments (new functionality: CloSegScan, include/clo_segscan.h) ----
+ * m = min(numel_seg, *num_in), the forms (CLO_HIP_SEGSCAN_COUNTS, CLO_HIP_SEGSCAN_OFFSETS), the inclusive ends e_r,
+ * count_size and num_out = e_(m-1) unclamped are clo_hip_expand's above. With n = numel rows of values_in, e_(-1) = 0,
+ * ct = min(e_(m-1), n) and b(i) the first row of the clipped segment [min(e_(r-1), n), min(e_r, n)) that holds row i:
+ * for every i < ct, data_out[i] = op over j in [b(i), i] of (sum type) values_in[j] when inclusive is 1, over [b(i), i)
+ * when it is 0, the identity at i = b(i) (0 for sum, the sum type's largest number for min, its smallest for max). op,
+ * the cast, value_type and sum_type (CloType numbers: int, uint, long or ulong, the sum at least as wide as the value)
+ * are clo_hip_reduce_by_key's. Rows i >= ct of data_out are not written.
+ * CLO_HIP_EARGS before anything is enqueued: an op, inclusive or form out of range, numel_seg or numel >= 2^32,
+ * counts_or_offsets NULL with numel_seg > 0 (offsets: always), values_in or data_out NULL with numel > 0, num_out NULL or
+ * misaligned, num_in misaligned, a pointer not aligned to its element, a missing or misaligned workspace with
+ * numel_seg > 0. Types and count sizes not built: CLO_HIP_EUNSUPPORTED. A workspace below
+ * clo_hip_segscan_workspace_bytes(numel_seg, numel): CLO_HIP_EWORKSPACE. data_out may be exactly values_in when the two
+ * types are equally wide; no other overlap of an output with an input, num_in or the other output is allowed (not
+ * checked here: the driver does). numel_seg 0 needs no workspace and writes *num_out = 0 alone. Whatever the arrays
+ * hold, reads stay inside the inputs, writes inside data_out[0, numel) and num_out, and the call completes.
+ * Launches: for the counts form the three of clo_hip_expand that write the ends into the workspace; one thread per tile
+ * boundary of the MERGE of the m clipped ends with the n row indices, which finds its split by a halving and writes
+ * num_out; one work-group per tile of clo_hip_segscan_tile merge steps that reduces the rows the tile takes after its
+ * last close; one work-group that scans the tiles' states; one work-group per tile that scans its steps from the
+ * tile's carry and writes its rows as one stretch. values_in is read once plus those open tails. No work-group waits
+ * for another and there are no global atomics; asynchronous on `stream`; nothing is allocated and the host never waits,
+ * so the call can be captured into a graph. clo_hip_segscan_tile: 0 for sizes not built.
+ * clo_hip_segscan_workspace_bytes is monotone in both arguments, 0 for (0, 0) and a multiple of
+ * CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_SEGSCAN_COUNTS 0
+#define CLO_HIP_SEGSCAN_OFFSETS 1
+size_t clo_hip_segscan_tile(int value_size, int sum_size);
+size_t clo_hip_segscan_workspace_bytes(size_t numel_seg, size_t numel);
+int clo_hip_segscan(int op, int inclusive, int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* values_in,
+	void* data_out, uint64_t* num_out, size_t numel_seg, size_t numel, int value_type, int sum_type,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
