@@ -1,5 +1,5 @@
 """The by-key sort, CloReduceByKey, CloScanByKey, CloHistogram, CloMerge, CloSearch, CloSetOp, CloSelect, CloTopK, CloExpand,
-CloSegReduce and CloSegSort on the queue production uses (no profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace
+CloSegReduce, CloSegSort and CloSegScan on the queue production uses (no profiling) and across queues. Every driver keeps its workspace behind a stream guard ("the workspace
 belongs to one queue at a time"): one object is called six times on two live queues in turn, with no host
 synchronisation between the calls and sizes that make it reuse and outgrow its workspace mid-sequence; then the queue of
 its last call is destroyed and the object is used on a third one, through the host-data and the device form. Last, the
@@ -16,6 +16,7 @@ from rbk_model import rbk
 from sbk_model import sbk
 from search_model import search
 from segreduce_model import segreduce
+from segscan_model import segscan
 from segsort_model import segsort
 from select_model import select
 from setop_model import setop
@@ -387,6 +388,32 @@ class _SegSort(_Expand):
         return ko, vo, np.array([total], np.uint64)
 
 
+class _SegScan(_Expand):
+    """The same counts over n uint values, the inclusive running sum in ulong: the ends' scan, the split, the tiles'
+    states and the carry scan talk through the object's workspace. -> (data_out, the total)."""
+    out_types = (np.uint64, np.uint64)
+
+    def new(self, clo, ctx):
+        return clo.SegScan("sum", "counts", ctx, "uint", "ulong", "uint", inclusive=True)
+
+    def inputs(self, n, seed):
+        return _segment_counts(n, seed), np.random.default_rng(seed + 1).integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+
+    def out_counts(self, ins):
+        return ins[1].size, 1
+
+    def call(self, obj, q, i, o, ins):
+        return obj.with_device_data(q, i[0], None, i[1], o[0], o[1], ins[0].size, ins[1].size)
+
+    def want(self, ins):
+        data, total = segscan("sum", "counts", ins[0], ins[1], "ulong", True)
+        return data, np.array([total], np.uint64)
+
+    def host(self, obj, q, ins):
+        data, total = obj.with_host_data(ins[0], ins[1], q_exec=q)
+        return data, np.array([total], np.uint64)
+
+
 def _same(got, want, what):
     assert len(got) == len(want)
     for k, (g, w) in enumerate(zip(got, want)):
@@ -395,7 +422,7 @@ def _same(got, want, what):
 
 
 @pytest.mark.parametrize("kind", [_SortByKey, _ReduceByKey, _ScanByKey, _Histogram, _Merge, _Search, _SetOp, _Select, _TopK, _TopKSortedArg, _Expand, _SegReduce,
-                                  _SegSort], ids=lambda k: k.__name__.strip("_"))
+                                  _SegSort, _SegScan], ids=lambda k: k.__name__.strip("_"))
 def test_object_moves_between_queues(gpu, kind):
     import cl_ops_amd as clo
     ctx, _ = gpu

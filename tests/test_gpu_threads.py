@@ -3,7 +3,7 @@ context: the threading contract of the reference (no locks, no mutable globals: 
 objects are independent — SURVEY §8b "Threading"). ctypes drops the GIL during a call, so the C drivers, their workspace
 caches and the run-time compiler really do run side by side here. Every result is checked bit for bit against numpy.
 The by-key sort, reduce by key, scan by key, histogram, merge, search, the set operations, select, top-k, expand, the
-segmented reduction and the segmented sort run the same way
+segmented reduction, the segmented sort and the segmented scan run the same way
 (the adapters of test_gpu_by_key_queues.py: inputs, the device call, the host-data call and the model of each), and
 give their device memory back like the sorters and scanners."""
 import threading
@@ -181,16 +181,17 @@ def test_topk_objects_on_distinct_threads(clo):
 
 
 def test_segmented_objects_on_distinct_threads(clo):
-    """Five threads in one process: an expand, a segmented reduction and a segmented sort (the ends' scan in each one's
-    workspace; the sort's second copy of the rows) next to one satradix sorter and one scanner."""
+    """Six threads in one process: an expand, a segmented reduction, a segmented sort and a segmented scan (the ends' scan
+    in each one's workspace; the sort's second copy of the rows; the scan's split and tile states) next to one satradix
+    sorter and one scanner."""
     import test_gpu_by_key_queues as K
     ctx = clo.Context(0)
     errors = []
     workers = [threading.Thread(target=_by_key_worker, args=(clo, ctx, kind, 80 + i, 16, 21, errors))
-               for i, kind in enumerate((K._Expand, K._SegReduce, K._SegSort))]
+               for i, kind in enumerate((K._Expand, K._SegReduce, K._SegSort, K._SegScan))]
     workers += [threading.Thread(target=_sort_worker, args=(clo, ctx, "satradix", "uint", 86, 16, 21, errors)),
                 threading.Thread(target=_scan_worker, args=(clo, ctx, "uint", "ulong", 87, 16, 21, errors))]
-    assert len(workers) == 5
+    assert len(workers) == 6
     for w in workers:
         w.start()
     for w in workers:
@@ -346,10 +347,10 @@ def test_topk_objects_give_their_device_memory_back(clo):
 
 
 def test_segmented_objects_give_their_device_memory_back(clo):
-    """And for an expand, a segmented reduction and a segmented sort: a cached workspace each, the sort's with a second
-    copy of the rows."""
+    """And for an expand, a segmented reduction, a segmented sort and a segmented scan: a cached workspace each, the
+    sort's with a second copy of the rows."""
     import test_gpu_by_key_queues as K
-    _give_back(clo, (K._Expand, K._SegReduce, K._SegSort))
+    _give_back(clo, (K._Expand, K._SegReduce, K._SegSort, K._SegScan))
 
 
 def _give_back(clo, kinds):

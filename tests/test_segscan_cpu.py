@@ -6,12 +6,14 @@ host stub answers the thin ABI's status-code table, and the C driver runs over t
 (tests/hoststub/*stub*.c, among them clo_hip_segscan_stub.c) under AddressSanitizer + UBSan, driven by the stand-alone
 program tests/segscan_host/segscan_host_test.c. The reference model the GPU tests compare against (segscan_model.py) is
 checked here against a plain Python loop over Python integers, and the strata of the GPU fuzz (segscan_strata.py) are
-shown to reach the tile edges they are there for."""
+shown to reach the tile edges they are there for; those of its second family (strata_lanes) the lanes and waves, seen
+through tests/segscan_lane_model.py."""
 import ctypes as C
 import glob
 import os
 import re
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
@@ -19,7 +21,8 @@ import pytest
 import cl_ops_amd as clo
 from cl_ops_amd.api import CLO_ERROR_ARGS
 from segscan_model import FORMS, NP, OPS, PAIRS, identity, merge_steps, segscan
-from segscan_strata import CLIPS, DISTS, NUM_INS, STRATA, strata
+from segscan_lane_model import ITEMS, WAVE, lanes
+from segscan_strata import CLIPS, DISTS, LANE_DISTS, LANE_ITEMS, LANE_STRATA, LANE_WAVE, NUM_INS, SEED, STRATA, strata, strata_lanes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -434,4 +437,46 @@ def test_the_fuzz_strata_reach_the_tile_edges():
     assert seen == dict(form=set(FORMS), count_type={"uint", "ulong"}, op=set(OPS), inclusive={False, True}, dist=set(DISTS),
                         clip=set(CLIPS), num_mode=set(NUM_INS))
     assert pairs == set(PAIRS)
+    assert all(v >= 1 for v in reach.values()), reach
+
+
+def test_the_lane_strata_reach_the_lanes_and_waves():
+    """What the second family of tests/test_gpu_segscan_fuzz.py runs, seen through the lane model: every value of every
+    dimension is dealt, in_place only where the widths match and in at least a quarter of the strata, n <= 3 T; among
+    them a lane with 17 closes, a wave of nothing but closes, a close on a lane's first and on a lane's last step, a
+    lane with no close, a tile without rows. The first family is what it was."""
+    T = clo.segscan_tile(4, 4)
+    assert (LANE_ITEMS, LANE_WAVE) == (ITEMS, WAVE) and SEED == 20231
+    first = strata(T)
+    assert len(first) == STRATA == 216 and "in_place" not in first[0]
+    digest = zlib.crc32(b"".join(s["src"].tobytes() + s["values"].tobytes() for s in first))
+    assert (sum(s["n"] for s in first), sum(s["m_h"] for s in first), digest) == (1330631, 235600, 3640288040)   # as before the second family
+    ss = strata_lanes(T)
+    assert len(ss) == LANE_STRATA == 96
+    seen = {k: set() for k in ("form", "count_type", "op", "inclusive", "dist", "clip", "num_mode", "in_place")}
+    pairs, placed = set(), 0
+    reach = dict(lane_of_closes=0, wave_of_closes=0, bit_0=0, bit_16=0, lane_without=0, tile_without_rows=0, above=0, below=0)
+    for s in ss:
+        for k in seen:
+            seen[k].add(s[k])
+        pairs.add((s["value_type"], s["sum_type"]))
+        assert s["n"] == s["values"].size <= 3 * T and s["values"].dtype == NP[s["value_type"]] and s["m_h"] <= 3 * T
+        same = np.dtype(NP[s["value_type"]]).itemsize == np.dtype(NP[s["sum_type"]]).itemsize
+        assert same or not s["in_place"]
+        placed += int(s["in_place"])
+        L = lanes(s["form"], s["src"], s["n"], T, s["num_in"], s["values"].dtype.itemsize)
+        close, m, total = merge_steps(s["form"], s["src"], s["n"], s["num_in"])
+        assert np.array_equal(L.na, np.bincount(close // T, minlength=L.tiles)[:L.tiles] if m else np.zeros(L.tiles, np.int64))
+        reach["lane_of_closes"] += int((L.ne == ITEMS).any())
+        reach["wave_of_closes"] += int((L.wave_closes == ITEMS * WAVE).any())
+        reach["bit_0"] += int((L.closes & 1).any())
+        reach["bit_16"] += int(((L.closes >> (ITEMS - 1)) & 1).any())
+        reach["lane_without"] += int(((L.ne == 0) & (L.steps == ITEMS)).any())
+        reach["tile_without_rows"] += int(((L.nb == 0) & (L.cnt > 0)).any())
+        reach["above"] += int(total > s["n"])
+        reach["below"] += int(total < s["n"])
+    assert seen == dict(form=set(FORMS), count_type={"uint", "ulong"}, op=set(OPS), inclusive={False, True}, dist=set(LANE_DISTS),
+                        clip=set(CLIPS), num_mode=set(NUM_INS), in_place={False, True})
+    assert pairs == set(PAIRS)
+    assert 4 * placed >= LANE_STRATA, placed
     assert all(v >= 1 for v in reach.values()), reach
