@@ -363,6 +363,36 @@ int clo_hip_select(int op, int pred, const void* keys_in, const void* values_in,
 	void* keys_out, void* values_out, uint64_t* num_out, size_t numel, int key_size, int key_kind,
 	int value_size, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- multi-way partition by bin (new functionality: CloBucket, include/clo_bucket.h) ----
+ * The bin of keys_in[i] is clo_hip_histogram's: with d = key - lower over the integers (lower: the low key_size bytes,
+ * key_signed: two's complement), the row is IN RANGE iff d >= 0 and (d >> shift) < num_bins, and its bin is d >> shift;
+ * every other row belongs to the rest, which counts as bin num_bins. The numel rows go to keys_out / values_out in
+ * ascending (bin, input index) order — a stable sort by bin, the rest last — and offsets_out receives num_bins + 1
+ * entries of count_size (4 or 8) bytes: offsets_out[b] = the rows in the bins below b, offsets_out[num_bins] = the rows
+ * in range. Values: value_size 0 (none), 4 or 8 opaque bytes; value_size 4 with values_in NULL writes the input row
+ * indices (uint32) and keys_out may then be NULL. numel 0 writes num_bins + 1 zeros and needs no workspace.
+ * CLO_HIP_EARGS: offsets_out NULL or misaligned, num_bins 0 or above CLO_HIP_BUCKET_MAX_BINS, numel >= 2^32, shift >= 8
+ * key_size, values passed with value_size 0, values_out NULL with value_size > 0, values_in NULL with value_size 8,
+ * keys_out NULL outside the index form, keys_in NULL with numel > 0, a misaligned array, a workspace that is NULL or not
+ * CLO_HIP_WORKSPACE_ALIGN aligned (numel > 0). Key sizes other than 1, 2, 4, 8, value sizes other than 0, 4, 8 and count
+ * sizes other than 4, 8: CLO_HIP_EUNSUPPORTED. A workspace below clo_hip_bucket_workspace_bytes(numel, key_size,
+ * value_size, num_bins): CLO_HIP_EWORKSPACE, nothing is launched. Nothing overlaps (the caller checks).
+ * Asynchronous on `stream`: one pass of five launches where num_bins + 1 <= 256 (count, the three launches of the
+ * counter scan, scatter), two such passes through the workspace plus clo_hip_histogram and a one-group scan above; no
+ * work-group waits for another, no host wait, so the calls record into a graph. Timing labels: "bucket_count",
+ * "bucket_scan", "bucket_scatter", "bucket_offsets". The counter scan gives CLO_HIP_BUCKET_SCAN_GROUP counters (digits of
+ * the pass x tiles) to a work-group and scans the groups' sums CLO_HIP_BUCKET_SCAN_TRIP per trip of its loop.
+ * clo_hip_bucket_tile: the rows per tile, 0 for sizes not built. clo_hip_bucket_workspace_bytes is monotone in numel and
+ * num_bins, 0 for numel 0 and a multiple of CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_BUCKET_MAX_BINS 65535
+#define CLO_HIP_BUCKET_SCAN_GROUP 4096
+#define CLO_HIP_BUCKET_SCAN_TRIP 2048
+size_t clo_hip_bucket_tile(int key_size, int value_size);
+size_t clo_hip_bucket_workspace_bytes(size_t numel, int key_size, int value_size, size_t num_bins);
+int clo_hip_bucket(const void* keys_in, const void* values_in, void* keys_out, void* values_out, void* offsets_out, size_t numel,
+	int key_size, int key_signed, int value_size, int count_size, uint64_t lower, unsigned shift, size_t num_bins,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- top-k (new functionality: CloTopK, include/clo_topk.h) ----
  * With m = min(k, numel): the first m elements of the stable ascending sort of keys_in[0, numel) (which
  * CLO_HIP_TOPK_SMALLEST) or of the stable sort by the complemented order key (CLO_HIP_TOPK_LARGEST: the largest key
