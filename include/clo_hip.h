@@ -575,6 +575,46 @@ int clo_hip_segscan(int op, int inclusive, int form, const void* counts_or_offse
 	void* data_out, uint64_t* num_out, size_t numel_seg, size_t numel, int value_type, int sum_type,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- arg-min and arg-max per segment (new functionality: CloSegArg, include/clo_segarg.h) ----
+ * m = min(numel_seg, *num_in), the forms (CLO_HIP_SEGARG_COUNTS, CLO_HIP_SEGARG_OFFSETS), the inclusive ends e_r,
+ * count_size and num_out = e_(m-1) unclamped are clo_hip_expand's above. value_type is a CloType number: int, uint, long,
+ * ulong, float or double. With n = numel rows of values_in, e_(-1) = 0 and x(i) the order key of values_in[i] (two's
+ * complement with the sign bit flipped, IEEE total order; complemented for CLO_HIP_SEGARG_ARGMAX), for every r < m whose
+ * range [min(e_(r-1), n), min(e_r, n)) holds a row: idx_out[r] = the row i of the range with the smallest x(i), among
+ * equal ones the smallest i (CLO_HIP_SEGARG_FIRST) or the largest (CLO_HIP_SEGARG_LAST), and val_out[r] = values_in[i]
+ * bit for bit. A range without a row: idx_out[r] = 0xffffffff and val_out[r] = the value whose key is all ones. Whether a
+ * range has a row is read from its ends. val_out may be NULL. Rows r >= m are not written.
+ * CLO_HIP_EARGS: an op, tie or form that is none of the numbers below, numel_seg or numel >= 2^32, a missing
+ * counts_or_offsets (numel_seg > 0, or the offsets form), values_in (numel > 0) or idx_out (numel_seg > 0), num_out NULL
+ * or misaligned, num_in misaligned, a pointer not aligned to its element, a missing or misaligned workspace with
+ * numel_seg > 0. Types and count sizes not built: CLO_HIP_EUNSUPPORTED. A workspace below
+ * clo_hip_segarg_workspace_bytes(numel_seg, numel): CLO_HIP_EWORKSPACE. No output may overlap an input, num_in or
+ * another output (not checked here: the driver does). numel_seg 0 needs no workspace and writes *num_out = 0 alone.
+ * Whatever the arrays hold, reads stay inside the inputs, writes inside idx_out[0, numel_seg), val_out[0, numel_seg)
+ * and num_out, and the call completes.
+ * Launches: clo_hip_segreduce's five stages with the aggregate (order key, index): the three that write the ends of the
+ * counts form; one thread per tile boundary of the merge of ends and rows; one work-group per tile of
+ * clo_hip_segarg_tile merge steps, which writes idx_out and val_out of every segment that closes in it and leaves its
+ * open aggregate, and what it holds of its first closing segment, in the workspace; one work-group that scans the
+ * tiles' open aggregates, clo_hip_segarg_carry_tiles of them per trip; one thread per tile that writes the tile's first
+ * closing segment from the carry and the tile's part. values_in is read once; val_out is decoded from the winning key,
+ * not gathered. No work-group waits for another and there are no global atomics; asynchronous on `stream`; nothing is
+ * allocated and the host never waits, so the call can be captured into a graph. clo_hip_segarg_tile: 0 for sizes not
+ * built. clo_hip_segarg_workspace_bytes is monotone in both arguments, 0 for (0, 0) and a multiple of
+ * CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_SEGARG_ARGMIN 0
+#define CLO_HIP_SEGARG_ARGMAX 1
+#define CLO_HIP_SEGARG_FIRST 0
+#define CLO_HIP_SEGARG_LAST 1
+#define CLO_HIP_SEGARG_COUNTS 0
+#define CLO_HIP_SEGARG_OFFSETS 1
+size_t clo_hip_segarg_tile(int value_size);
+size_t clo_hip_segarg_carry_tiles(void);
+size_t clo_hip_segarg_workspace_bytes(size_t numel_seg, size_t numel);
+int clo_hip_segarg(int op, int tie, int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* values_in,
+	uint32_t* idx_out, void* val_out, uint64_t* num_out, size_t numel_seg, size_t numel, int value_type,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----
