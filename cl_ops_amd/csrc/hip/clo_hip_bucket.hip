@@ -11,7 +11,7 @@
 // A pass is five launches, none of which waits for another work-group, none of which uses a global atomic (§10):
 //   COUNT    one work-group per tile of 4096 rows counts its digits in LDS and writes them DIGIT-major:
 //            counter[digit * tiles + tile], for the digits the pass has;
-//   SUMS, SUMS_SCAN, ENDS   the shared three-launch scan of clo_hip_op_device.h over the digits * tiles counters (the
+//   SUMS, SUMS_SCAN, ENDS   the shared three-launch scan of clo_hip_seg_device.h over the digits * tiles counters (the
 //            inclusive ends in 64 bits; a group takes CLO_HIP_BUCKET_SCAN_GROUP counters, the one-group scan of the
 //            groups' sums CLO_HIP_BUCKET_SCAN_TRIP sums per trip);
 //   SCATTER  re-reads the tile, ranks its rows stably on chip and writes keys, values or indices to
@@ -29,7 +29,7 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
-#include "clo_hip_op_device.h"
+#include "clo_hip_seg_device.h"
 
 namespace {
 
@@ -101,7 +101,8 @@ void clo_bucket_count_kernel(const TK* __restrict__ keys, size_t n, bkt_map<TK> 
 	if (tid < digits) counter[(size_t) tid * tiles + blockIdx.x] = s_cnt[tid];
 }
 
-// ---- 2. the scan of the digits * tiles counters (clo_hip_op_device.h) ----
+// ---- 2. the scan of the digits * tiles counters (clo_hip_seg_device.h). The kernels take neither num_in nor vec_ok and
+// the three launches share ONE timing label, so the host launches them here and not through clo_op_ends_launch ----
 __global__ __launch_bounds__(BKT_THREADS)
 void clo_bucket_sums_kernel(const unsigned* __restrict__ counter, unsigned m_h, clo_op_u64* __restrict__ tsum) {
 	clo_op_ends_sums<unsigned>(counter, nullptr, m_h, 1, tsum);

@@ -27,7 +27,7 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
-#include "clo_hip_op_device.h"
+#include "clo_hip_seg_device.h"
 
 namespace {
 
@@ -35,7 +35,7 @@ typedef unsigned long long exp_u64;
 
 constexpr int EXP_THREADS = 256;
 constexpr int EXP_WAVES = EXP_THREADS / 64;
-static_assert(EXP_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS");
+static_assert(EXP_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS, and clo_op_ends_launch launches groups of it");
 constexpr unsigned EXP_TILE_LOG2 = 12;
 constexpr unsigned EXP_TILE = 1u << EXP_TILE_LOG2;               // T: output rows per tile, for every value size
 constexpr unsigned EXP_PER_THREAD = EXP_TILE / EXP_THREADS;      // 16 consecutive rows of the max scan
@@ -66,7 +66,7 @@ __device__ __forceinline__ void exp_halve(const E& e, unsigned (&base)[N], unsig
 	}
 }
 
-// ---- 1. the ends of the counts form: the three launches of clo_hip_op_device.h ----
+// ---- 1. the ends of the counts form: the three launches of clo_hip_seg_device.h ----
 
 template <typename TC>
 __global__ __launch_bounds__(EXP_THREADS)
@@ -224,32 +224,13 @@ struct exp_args {
 
 inline unsigned exp_tiles(size_t capacity) { return (unsigned) ((capacity + EXP_TILE - 1) / EXP_TILE); }
 
-template <typename TC>
-int exp_ends_launch(const exp_args& a) {
-	const unsigned tiles = (unsigned) clo_op_ends_tiles(a.m_h);
-	const int vec_ok = clo_op_vec_ok<TC>(a.src);
-	{
-		clo_timing_scope timing("expand_sums", a.s);
-		hipLaunchKernelGGL((clo_expand_sums_kernel<TC>), dim3(tiles), dim3(EXP_THREADS), 0, a.s, (const TC*) a.src, a.num_in, a.m_h, vec_ok, a.tsum);
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return (int) e;
-	}
-	{
-		clo_timing_scope timing("expand_sums_scan", a.s);
-		hipLaunchKernelGGL(clo_expand_sums_scan_kernel, dim3(1), dim3(EXP_THREADS), 0, a.s, a.tsum, tiles);
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return (int) e;
-	}
-	clo_timing_scope timing("expand_ends", a.s);
-	hipLaunchKernelGGL((clo_expand_ends_kernel<TC>), dim3(tiles), dim3(EXP_THREADS), 0, a.s, (const TC*) a.src, a.num_in, a.m_h, vec_ok,
-		(const exp_u64*) a.tsum, a.ends);
-	return (int) hipGetLastError();
-}
+constexpr const char* EXP_ENDS_LABELS[3] = { "expand_sums", "expand_sums_scan", "expand_ends" };
 
 template <typename TC, bool OFFSETS, typename TV>
 int exp_launch(const exp_args& a) {
 	if constexpr (!OFFSETS) {
-		const int st = exp_ends_launch<TC>(a);
+		const int st = clo_op_ends_launch<TC>(clo_expand_sums_kernel<TC>, clo_expand_sums_scan_kernel, clo_expand_ends_kernel<TC>, EXP_ENDS_LABELS,
+			a.src, a.num_in, a.m_h, a.tsum, a.ends, a.s);
 		if (st != 0) return st;
 	}
 	const unsigned tiles = exp_tiles(a.capacity);

@@ -1,7 +1,9 @@
 // clo_hip_op_device.h — what the kernels of the operations that are not upstream share (clo_hip_rbk, sbk, merge,
-// search, setop, select, topk, hist, expand, segreduce and segsort .hip). Each piece is here once because its copies were the same
-// text, or differed only by a parameter a copy had fixed; what differs on purpose stays in its file. Everything has
-// internal linkage, and every __global__ function stays in its own file under its own name.
+// search, setop, select, topk, hist, expand, segreduce, segsort, segscan, bucket and segarg .hip). Each
+// piece is here once because its copies were the same text, or differed only by a parameter a copy had fixed; what
+// differs on purpose stays in its file. Everything has internal linkage, and every __global__ function stays in its own
+// file under its own name. The 64-bit segment ends and the merge path of the operations over segments from counts or
+// offsets are in clo_hip_seg_device.h, which includes this header.
 #ifndef CLO_HIP_OP_DEVICE_H
 #define CLO_HIP_OP_DEVICE_H
 
@@ -331,166 +333,6 @@ __device__ __forceinline__ clo_op_seg_state<TS> clo_op_seg_scan_pieces(const uns
 	total->h = clo_op_readlane<unsigned>(incl.h, 63u);
 	total->a = AGG ? clo_op_readlane<TS>(incl.a, 63u) : (TS) 0;
 	return clo_op_seg_wave_exclusive<OP, AGG, TS>(incl, lane);
-}
-
-// ---- the 64-bit segment ends of counts or offsets (expand, segreduce, segsort) ----
-
-typedef unsigned long long clo_op_u64;
-
-constexpr int CLO_OP_WAVES = CLO_OP_THREADS / 64;
-constexpr int CLO_OP_ROW_ELEMS = CLO_OP_THREADS * CLO_OP_VEC;            // 1024 counts: one coalesced stretch
-constexpr int CLO_OP_ENDS_ROWS = 4;
-constexpr unsigned CLO_OP_ENDS_TILE = CLO_OP_ENDS_ROWS * CLO_OP_ROW_ELEMS;   // counts per tile of the ends' scan
-constexpr unsigned CLO_OP_SUMS_ITEMS = 8;
-constexpr unsigned CLO_OP_SUMS_TRIP = CLO_OP_THREADS * CLO_OP_SUMS_ITEMS;    // tile sums per trip of the one-group scan
-inline size_t clo_op_ends_tiles(size_t m_h) { return (m_h + CLO_OP_ENDS_TILE - 1) / CLO_OP_ENDS_TILE; }
-
-// m = min(m_h, *num_in)
-__device__ __forceinline__ unsigned clo_op_segments(const clo_op_u64* __restrict__ num_in, unsigned m_h) {
-	if (!num_in) return m_h;
-	const clo_op_u64 v = *num_in;
-	return v < m_h ? (unsigned) v : m_h;
-}
-
-// Where the inclusive ends are: the workspace (counts form) or the offsets themselves, rebased. at(r) needs r < m_h.
-template <typename TC, bool OFFSETS>
-struct clo_op_ends {
-	const TC* off; const clo_op_u64* ends; clo_op_u64 base;
-	__device__ __forceinline__ clo_op_u64 at(unsigned r) const {
-		if constexpr (OFFSETS) return (clo_op_u64) off[(size_t) r + 1u] - base;
-		else return ends[r];
-	}
-};
-
-template <typename TC, bool OFFSETS>
-__device__ __forceinline__ clo_op_ends<TC, OFFSETS> clo_op_ends_make(const TC* __restrict__ src, const clo_op_u64* __restrict__ ends) {   // m_h > 0
-	clo_op_ends<TC, OFFSETS> e;
-	e.off = src; e.ends = ends;
-	e.base = OFFSETS ? (clo_op_u64) src[0] : 0ull;
-	return e;
-}
-
-// the tile's counts as 64-bit numbers, those at r >= m as 0: row by row, four consecutive ones per lane
-template <typename TC>
-__device__ __forceinline__ void clo_op_ends_load_counts(const TC* __restrict__ counts, size_t i0, unsigned m_h, unsigned m, bool vec_ok,
-	clo_op_u64 (&c)[CLO_OP_VEC]) {
-	TC raw[CLO_OP_VEC];
-	clo_op_load4<TC>(counts, i0, m_h, vec_ok, raw);
-	#pragma unroll
-	for (int k = 0; k < CLO_OP_VEC; ++k) c[k] = i0 + k < m ? (clo_op_u64) raw[k] : 0ull;
-}
-
-// The bodies of the three launches that write the m_h inclusive ends of the counts form (CloSelect's count scan, in 64
-// bits); the __global__ functions that call them stay in the operations' files. 1: the sum of every tile of
-// CLO_OP_ENDS_TILE counts.
-template <typename TC>
-__device__ __forceinline__ void clo_op_ends_sums(const TC* __restrict__ counts, const clo_op_u64* __restrict__ num_in, unsigned m_h, int vec_ok,
-	clo_op_u64* __restrict__ tsum) {
-	__shared__ clo_op_u64 s_wave[CLO_OP_WAVES];
-	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const unsigned m = clo_op_segments(num_in, m_h);
-	const size_t base = (size_t) blockIdx.x * CLO_OP_ENDS_TILE + (size_t) tid * CLO_OP_VEC;
-	clo_op_u64 sum = 0;
-	#pragma unroll
-	for (int r = 0; r < CLO_OP_ENDS_ROWS; ++r) {
-		clo_op_u64 c[CLO_OP_VEC];
-		clo_op_ends_load_counts<TC>(counts, base + (size_t) r * CLO_OP_ROW_ELEMS, m_h, m, vec_ok != 0, c);
-		sum += c[0] + c[1] + c[2] + c[3];
-	}
-	sum = clo_wave_reduce_sum<clo_op_u64>(sum);
-	if (lane == 0) s_wave[wave] = sum;
-	__syncthreads();
-	if (tid == 0) tsum[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-}
-
-// 2: tsum[0, tiles) -> its exclusive sums in place (modulo 2^64). One work-group; the next trip's sums are requested
-// before this trip's are added.
-__device__ __forceinline__ void clo_op_ends_sums_scan(clo_op_u64* __restrict__ tsum, unsigned tiles) {
-	__shared__ clo_op_u64 s_wave[CLO_OP_WAVES];
-	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	clo_op_u64 carry = 0;
-	clo_op_u64 v[CLO_OP_SUMS_ITEMS], ahead[CLO_OP_SUMS_ITEMS];
-	#pragma unroll
-	for (unsigned c = 0; c < CLO_OP_SUMS_ITEMS; ++c) {
-		const unsigned i = tid * CLO_OP_SUMS_ITEMS + c;
-		ahead[c] = i < tiles ? tsum[i] : 0ull;
-	}
-	for (unsigned base = 0; base < tiles; base += CLO_OP_SUMS_TRIP) {   // tiles <= 2^20: no wrap
-		clo_op_u64 sum = 0;
-		#pragma unroll
-		for (unsigned c = 0; c < CLO_OP_SUMS_ITEMS; ++c) {
-			v[c] = ahead[c];
-			sum += v[c];
-			const unsigned i = base + CLO_OP_SUMS_TRIP + tid * CLO_OP_SUMS_ITEMS + c;
-			ahead[c] = i < tiles ? tsum[i] : 0ull;
-		}
-		const clo_op_u64 incl = clo_wave_scan_inclusive<clo_op_u64>(sum, lane);
-		if (lane == 63u) s_wave[wave] = incl;
-		__syncthreads();
-		clo_op_u64 before = 0, total = 0;
-		#pragma unroll
-		for (unsigned w = 0; w < (unsigned) CLO_OP_WAVES; ++w) {
-			const clo_op_u64 s = s_wave[w];
-			if (w < wave) before += s;
-			total += s;
-		}
-		clo_op_u64 at = carry + before + incl - sum;
-		#pragma unroll
-		for (unsigned c = 0; c < CLO_OP_SUMS_ITEMS; ++c) {
-			const unsigned i = base + tid * CLO_OP_SUMS_ITEMS + c;
-			if (i < tiles) tsum[i] = at;
-			at += v[c];
-		}
-		carry += total;
-		__syncthreads();   // s_wave is written again
-	}
-}
-
-// 3: the tiles' ends, ends[r] for every r < m_h
-template <typename TC>
-__device__ __forceinline__ void clo_op_ends_write(const TC* __restrict__ counts, const clo_op_u64* __restrict__ num_in, unsigned m_h, int vec_ok,
-	const clo_op_u64* __restrict__ tsum, clo_op_u64* __restrict__ ends) {
-	constexpr int PIECES = CLO_OP_ENDS_ROWS * CLO_OP_WAVES;
-	__shared__ clo_op_u64 s_piece[PIECES];
-	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const unsigned m = clo_op_segments(num_in, m_h);
-	const size_t base = (size_t) blockIdx.x * CLO_OP_ENDS_TILE + (size_t) tid * CLO_OP_VEC;
-	clo_op_u64 c[CLO_OP_ENDS_ROWS][CLO_OP_VEC], before[CLO_OP_ENDS_ROWS];
-	#pragma unroll
-	for (int r = 0; r < CLO_OP_ENDS_ROWS; ++r) {
-		clo_op_ends_load_counts<TC>(counts, base + (size_t) r * CLO_OP_ROW_ELEMS, m_h, m, vec_ok != 0, c[r]);
-		const clo_op_u64 t = c[r][0] + c[r][1] + c[r][2] + c[r][3];
-		const clo_op_u64 incl = clo_wave_scan_inclusive<clo_op_u64>(t, lane);
-		before[r] = incl - t;
-		if (lane == 63u) s_piece[r * CLO_OP_WAVES + (int) wave] = incl;
-	}
-	__syncthreads();
-	clo_op_u64 at = tsum[blockIdx.x];
-	#pragma unroll
-	for (int r = 0; r < CLO_OP_ENDS_ROWS; ++r) {
-		#pragma unroll
-		for (int w = 0; w < CLO_OP_WAVES; ++w) {
-			const clo_op_u64 p = s_piece[r * CLO_OP_WAVES + w];
-			if ((unsigned) w < wave) before[r] += p;
-		}
-		const size_t i0 = base + (size_t) r * CLO_OP_ROW_ELEMS;
-		clo_op_u64 e[CLO_OP_VEC];
-		clo_op_u64 run = at + before[r];
-		#pragma unroll
-		for (int k = 0; k < CLO_OP_VEC; ++k) { run += c[r][k]; e[k] = run; }
-		if (i0 + CLO_OP_VEC <= m_h) {   // the workspace is 256-byte aligned and i0 a multiple of 4
-			typedef clo_op_u64 vec2 __attribute__((ext_vector_type(2)));
-			vec2 a, b;
-			a.x = e[0]; a.y = e[1]; b.x = e[2]; b.y = e[3];
-			*reinterpret_cast<vec2*>(ends + i0) = a;
-			*reinterpret_cast<vec2*>(ends + i0 + 2) = b;
-		} else {
-			#pragma unroll
-			for (int k = 0; k < CLO_OP_VEC; ++k) if (i0 + k < m_h) ends[i0 + k] = e[k];
-		}
-		#pragma unroll
-		for (int w = 0; w < CLO_OP_WAVES; ++w) at += s_piece[r * CLO_OP_WAVES + w];
-	}
 }
 
 }  // namespace

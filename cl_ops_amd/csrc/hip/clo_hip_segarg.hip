@@ -4,8 +4,8 @@
 //     idx_out[r] = the row i in [min(e_(r-1), n), min(e_r, n)) with the smallest (x(i), i) for `first`, (x(i), ~i) for `last`,
 //     val_out[r] = values_in[idx_out[r]];     CLO_SEGARG_NONE and the key that comes last in the order without a row.
 //
-// The schedule is clo_hip_segreduce.hip's (§21), launch by launch: ENDS (counts form), PARTITION, SWEEP, CARRY, FIXUP.
-// No launch waits for another work-group, none uses a global atomic. What differs:
+// The schedule is the merge path of clo_hip_seg_device.h, which has its argument and the bounds of every read, with
+// CloSegReduce's launches (§21): ENDS (counts form), PARTITION, SWEEP, CARRY, FIXUP. What is this file's:
 //   the aggregate  is (order key, j) with j = i for `first` and ~i for `last`, the smaller of two winning and the LEFT one on
 //                  full equality. 4-byte values: one 64-bit word (x << 32) | j under an unsigned minimum. 8-byte values:
 //                  a 64-bit key and a 32-bit j compared lexicographically. A row's index is where it lies in the merge
@@ -22,36 +22,21 @@
 //                  identity is that row's own word.
 //   the fix-up     rewrites the first segment that closes in every tile from (the carry into the tile) min (what the tile
 //                  holds of it), the latter left in the workspace by the sweep: an index does not say what key it had.
-// Whatever the arrays hold: §21's argument for the reads (halvings over shrinking ranges, ends at indices below m, rows
-// [b0, b0 + nb) with b0 + nb <= n, positions clamped to [0, nb]); a lane closes at most na = a1 - a0 segments, so every
-// write lands in idx_out[a0, a1) and val_out[a0, a1), a1 <= m; the fix-up writes row tile_first < a1 <= m; val_out is
-// decoded from a key, so a wrong index is never dereferenced.
+// A lane closes at most na = a1 - a0 segments, so every write lands in idx_out[a0, a1) and val_out[a0, a1), a1 <= m; the
+// fix-up writes row tile_first < a1 <= m; val_out is decoded from a key, so a wrong index is never dereferenced.
 #include <hip/hip_runtime.h>
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
-#include "clo_hip_op_device.h"
+#include "clo_hip_seg_device.h"
 
 namespace {
 
 typedef clo_op_u64 arg_u64;
 
-constexpr int ARG_THREADS = 256;
-constexpr int ARG_WAVES = ARG_THREADS / 64;
-static_assert(ARG_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS");
-constexpr int ARG_ITEMS = 17;                                   // merge steps per lane: odd, so that the lanes' LDS reads spread over the banks
-constexpr unsigned ARG_TILE = ARG_THREADS * ARG_ITEMS;          // T = 4352 merge steps, for both value sizes
 constexpr unsigned ARG_NOPOS = 0xffffu;                         // a closing segment without a row, among the 16-bit positions
-static_assert(ARG_TILE < ARG_NOPOS, "a row's position in its tile is kept in 16 bits, and one value says `none`");
+static_assert(CLO_SEG_TILE < ARG_NOPOS, "a row's position in its tile is kept in 16 bits, and one value says `none`");
 constexpr unsigned ARG_NONE = 0xffffffffu;                      // CLO_SEGARG_NONE; also: a tile in which no segment closes
-constexpr int ARG_CARRY_ITEMS = 16;
-static_assert(ARG_CARRY_ITEMS % 4 == 0, "a thread's states are loaded four and two at a time");
-constexpr unsigned ARG_CARRY_TRIP = ARG_THREADS * ARG_CARRY_ITEMS;   // tile states per trip of the one-group scan
-
-inline size_t arg_tiles(size_t numel_seg, size_t numel) { return (numel_seg + numel + ARG_TILE - 1) / ARG_TILE; }
-
-__device__ __forceinline__ arg_u64 arg_min64(arg_u64 a, arg_u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ arg_u64 arg_max64(arg_u64 a, arg_u64 b) { return a > b ? a : b; }
 
 // ---- the aggregate: (order key, j), the smaller wins, the left one on full equality ----
 template <int VS> struct arg_agg;
@@ -134,14 +119,14 @@ __device__ __forceinline__ arg_state<A> arg_wave_exclusive(const arg_state<A>& i
 // the states of the work-group's waves in LDS: what lies before this wave, and all of them, from `from`
 template <typename A>
 struct arg_waves {
-	unsigned h[ARG_WAVES]; arg_u64 x[ARG_WAVES]; unsigned j[ARG_WAVES];
+	unsigned h[CLO_SEG_WAVES]; arg_u64 x[CLO_SEG_WAVES]; unsigned j[CLO_SEG_WAVES];
 	__device__ __forceinline__ void put(unsigned wave, const arg_state<A>& s) { h[wave] = s.h; x[wave] = s.a.word(); j[wave] = s.a.j(); }
 	struct both { arg_state<A> before, all; };
 	__device__ __forceinline__ both get(unsigned wave, const arg_state<A>& from) const {
 		both o;
 		o.before = from; o.all = from;
 		#pragma unroll
-		for (unsigned w = 0; w < (unsigned) ARG_WAVES; ++w) {
+		for (unsigned w = 0; w < (unsigned) CLO_SEG_WAVES; ++w) {
 			arg_state<A> p;
 			p.h = h[w]; p.a = A::words(x[w], j[w]);
 			if (w < wave) o.before = arg_combine<A>(o.before, p);
@@ -161,43 +146,30 @@ __device__ __forceinline__ TV arg_key_of(TV v, const arg_key& k) { return (TV) (
 template <typename TV>
 __device__ __forceinline__ TV arg_value_of(TV x, const arg_key& k) { return clo_keyx_inv<TV>((TV) (x ^ (TV) k.cmpl), k.kx); }
 
-// ---- 1. the ends of the counts form: the three launches of clo_hip_op_device.h ----
+// ---- 1. the ends of the counts form: the three launches of clo_hip_seg_device.h ----
 
 template <typename TC>
-__global__ __launch_bounds__(ARG_THREADS)
+__global__ __launch_bounds__(CLO_SEG_THREADS)
 void clo_segarg_sums_kernel(const TC* __restrict__ counts, const arg_u64* __restrict__ num_in, unsigned m_h, int vec_ok, arg_u64* __restrict__ tsum) {
 	clo_op_ends_sums<TC>(counts, num_in, m_h, vec_ok, tsum);
 }
 
-__global__ __launch_bounds__(ARG_THREADS)
+__global__ __launch_bounds__(CLO_SEG_THREADS)
 void clo_segarg_sums_scan_kernel(arg_u64* __restrict__ tsum, unsigned tiles) { clo_op_ends_sums_scan(tsum, tiles); }
 
 template <typename TC>
-__global__ __launch_bounds__(ARG_THREADS)
+__global__ __launch_bounds__(CLO_SEG_THREADS)
 void clo_segarg_ends_kernel(const TC* __restrict__ counts, const arg_u64* __restrict__ num_in, unsigned m_h, int vec_ok,
 	const arg_u64* __restrict__ tsum, arg_u64* __restrict__ ends) {
 	clo_op_ends_write<TC>(counts, num_in, m_h, vec_ok, tsum, ends);
 }
 
 // ---- 2. partition ----
-// split[t] = how many of the first d = min(t * T, m + n) merge steps close a segment; in [max(0, d - n), min(d, m)].
 template <typename TC, bool OFFSETS>
-__global__ __launch_bounds__(ARG_THREADS)
+__global__ __launch_bounds__(CLO_SEG_THREADS)
 void clo_segarg_partition_kernel(const TC* __restrict__ src, const arg_u64* __restrict__ ends, const arg_u64* __restrict__ num_in, unsigned m_h,
 	unsigned n, unsigned tiles, unsigned* __restrict__ split, arg_u64* __restrict__ num_out) {
-	const unsigned t = blockIdx.x * ARG_THREADS + threadIdx.x;
-	if (t > tiles) return;
-	const unsigned m = clo_op_segments(num_in, m_h);
-	const clo_op_ends<TC, OFFSETS> e = clo_op_ends_make<TC, OFFSETS>(src, ends);
-	const arg_u64 d = arg_min64((arg_u64) t * ARG_TILE, (arg_u64) m + n);
-	unsigned lo = d > n ? (unsigned) (d - n) : 0u, hi = (unsigned) arg_min64(d, m);
-	while (lo < hi) {   // at most 32 trips: hi - lo halves
-		const unsigned mid = lo + ((hi - lo) >> 1);   // < hi <= m
-		const arg_u64 c = arg_min64(e.at(mid), n);
-		if (c <= d - 1u - mid) lo = mid + 1u; else hi = mid;
-	}
-	split[t] = lo;
-	if (t == 0) *num_out = m > 0u ? e.at(m - 1u) : 0ull;
+	clo_seg_partition<TC, OFFSETS>(src, ends, num_in, m_h, n, tiles, split, num_out);
 }
 
 // numel_seg 0: there is nothing to read
@@ -215,88 +187,53 @@ struct arg_tile_ws {
 
 // ---- 3. tile sweep ----
 template <typename TC, bool OFFSETS, int VS, bool LAST>
-__global__ __launch_bounds__(ARG_THREADS)
+__global__ __launch_bounds__(CLO_SEG_THREADS)
 void clo_segarg_sweep_kernel(const TC* __restrict__ src, const arg_u64* __restrict__ ends, const arg_u64* __restrict__ num_in, unsigned m_h, unsigned n,
 	const unsigned* __restrict__ split, const typename arg_agg<VS>::TV* __restrict__ values, unsigned* __restrict__ idx_out,
 	typename arg_agg<VS>::TV* __restrict__ val_out, arg_key key, arg_tile_ws tw) {
 	typedef arg_agg<VS> A;
 	typedef typename A::TV TV;
 	// the tile's rows as they lie in memory until the lanes have walked them, then the values of its segments
-	__shared__ __attribute__((aligned(16))) TV s_val[ARG_TILE];
+	__shared__ __attribute__((aligned(16))) TV s_val[CLO_SEG_TILE];
 	// the ends' positions in [0, nb], nb <= T, until the lanes know their steps; then the winning rows' positions
-	__shared__ unsigned short s_end[ARG_TILE];
-	__shared__ unsigned s_start[ARG_THREADS + 1];
+	__shared__ unsigned short s_end[CLO_SEG_TILE];
+	__shared__ unsigned s_start[CLO_SEG_THREADS + 1];
 	__shared__ arg_waves<A> s_waves;
 	__shared__ arg_u64 s_px;
 	__shared__ unsigned s_pj;
 	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
 	const unsigned m = clo_op_segments(num_in, m_h);
 
-	// the tile's steps [d0, d1), of which [a0, a1) close segments and the rest take rows [b0, b0 + nb): the split clamped
-	const arg_u64 total = (arg_u64) m + n, dd0 = (arg_u64) blockIdx.x * ARG_TILE;
-	const arg_u64 d0 = arg_min64(dd0, total), d1 = arg_min64(dd0 + ARG_TILE, total);
-	const unsigned cnt = (unsigned) (d1 - d0);
-	if (cnt == 0u) {   // the whole work-group: beyond the last step (m < numel_seg)
+	const clo_seg_steps st = clo_seg_tile_steps(m, n);
+	if (st.cnt == 0u) {   // the whole work-group: beyond the last step (m < numel_seg)
 		if (tid == 0u) { tw.h[blockIdx.x] = 0u; tw.first[blockIdx.x] = ARG_NONE; tw.ax[blockIdx.x] = ~0ull; tw.aj[blockIdx.x] = ~0u; }
 		return;
 	}
-	arg_u64 a0w = split[blockIdx.x], a1w = split[blockIdx.x + 1u];
-	a0w = arg_min64(arg_max64(a0w, d0 > n ? d0 - n : 0ull), arg_min64(d0, m));
-	a1w = arg_min64(arg_max64(a1w, arg_max64(a0w, d1 > n ? d1 - n : 0ull)), arg_min64(m, a0w + cnt));
-	const unsigned a0 = (unsigned) a0w, na = (unsigned) (a1w - a0w), nb = cnt - na;
-	const arg_u64 b0 = d0 - a0w;   // b0 + nb = d1 - a1 <= n
+	const clo_seg_range g = clo_seg_tile_clamp(st, split, m, n);
+	const unsigned a0 = g.a0, na = g.na;
+	const arg_u64 b0 = g.b0;
 
 	clo_keyx raw_kx;
 	raw_kx.sign = 0; raw_kx.field = 0; raw_kx.kind = 0;   // (not looked at: the rows are staged as they are)
-	clo_op_stage<TV, false>(values + b0, nb, s_val, raw_kx, tid);
-	if (na > 0u) {
-		const clo_op_ends<TC, OFFSETS> e = clo_op_ends_make<TC, OFFSETS>(src, ends);
-		for (unsigned k = tid; k < na; k += ARG_THREADS) {
-			const arg_u64 c = arg_min64(e.at(a0 + k), n);   // a0 + k < a1 <= m
-			s_end[k] = (unsigned short) (c < b0 ? 0u : (unsigned) arg_min64(c - b0, nb));
-		}
-	}
+	clo_op_stage<TV, false>(values + b0, g.nb, s_val, raw_kx, tid);
+	if (na > 0u) clo_seg_stage_ends<TC, OFFSETS>(clo_op_ends_make<TC, OFFSETS>(src, ends), g, n, s_end, tid);
 	__syncthreads();
-
-	// where this lane's steps begin: of the first d steps of the tile, `a` close a segment
-	const unsigned d = clo_op_min(tid * ARG_ITEMS, cnt);
-	unsigned a, b;
-	{
-		unsigned lo = d > nb ? d - nb : 0u, hi = clo_op_min(d, na);
-		while (lo < hi) {
-			const unsigned mid = lo + ((hi - lo) >> 1);
-			if (s_end[mid] <= d - 1u - mid) lo = mid + 1u; else hi = mid;
-		}
-		a = lo; b = d - lo;
-	}
-	const unsigned a_lane = a;
-	// the lane closes the ends [a, the next lane's a) and takes the rows between them; end a + j closes at step
-	// j + (the lane's rows before it), whatever the other ends are
-	s_start[tid] = a;
-	if (tid == 0u) s_start[ARG_THREADS] = na;
-	__syncthreads();
-	const unsigned steps = clo_op_min((unsigned) ARG_ITEMS, cnt - d);
-	const unsigned ne = clo_op_min(clo_op_max(s_start[tid + 1u], a) - a, steps);
-	const unsigned nr = steps - ne;   // its rows [b, b + nr); b + nr <= nb
-	unsigned closes = 0u;             // bit k = step k closes a segment
-	unsigned has_row = 0u;            // bit j = the lane's j-th closing segment has a row in the tile: its end lies behind the end before it
-	unsigned before = a > 0u ? s_end[clo_op_min(a - 1u, ARG_TILE - 1u)] : 0u;   // (the tile's first segment: behind the tile's first row)
-	#pragma unroll
-	for (int j = 0; j < ARG_ITEMS; ++j) {
-		const unsigned ea = s_end[clo_op_min(a + (unsigned) j, ARG_TILE - 1u)];
-		const unsigned p = clo_op_min(ea > b ? ea - b : 0u, nr) + (unsigned) j;   // < steps where j < ne
-		closes |= ((unsigned) j < ne ? 1u : 0u) << (p & 31u);
+	clo_seg_lane l = clo_seg_lane_begin(g, s_end, s_start, tid);
+	unsigned has_row = 0u;   // bit j = the lane's j-th closing segment has a row in the tile: its end lies behind the end before it
+	unsigned before = l.a > 0u ? s_end[clo_op_min(l.a - 1u, CLO_SEG_TILE - 1u)] : 0u;   // (the tile's first segment: behind the tile's first row)
+	clo_seg_lane_closes(l, s_end, [&](int j, unsigned ea) {
 		has_row |= (ea > before ? 1u : 0u) << j;
 		before = ea;
-	}
+	});
+	const unsigned b = l.b, steps = l.steps, closes = l.closes;
 	// x[k] = (key, j) of the row step k takes, the identity where it takes none: 17 reads that do not wait for each other
-	A x[ARG_ITEMS];
+	A x[CLO_SEG_ITEMS];
 	arg_state<A> s = arg_empty<A>();
 	#pragma unroll
-	for (int k = 0; k < ARG_ITEMS; ++k) {
+	for (int k = 0; k < CLO_SEG_ITEMS; ++k) {
 		const bool close = (closes >> k) & 1u;
 		const unsigned rs = (unsigned) k - (unsigned) __popc(closes & ((1u << k) - 1u));
-		const TV raw = s_val[clo_op_min(b + rs, ARG_TILE - 1u)];
+		const TV raw = s_val[clo_op_min(b + rs, CLO_SEG_TILE - 1u)];
 		const unsigned i = (unsigned) b0 + b + rs;   // the row's index in values_in: < n where the step takes a row
 		x[k] = (!close && (unsigned) k < steps) ? A::make(arg_key_of<TV>(raw, key), LAST ? ~i : i) : A::identity();
 		s.h += close ? 1u : 0u;
@@ -320,11 +257,11 @@ void clo_segarg_sweep_kernel(const TC* __restrict__ src, const arg_u64* __restri
 
 	// the walk again, from registers, with what was open before the lane: a close stores the segment's winner
 	A open = in.a;
-	unsigned at = a_lane;   // a step closes at most ne times, and a_lane + ne <= na
+	unsigned at = l.a;   // a step closes at most ne times, and l.a + ne <= na
 	unsigned nth = 0u;
 	const TV none_val = arg_value_of<TV>((TV) ~(TV) 0, key);
 	#pragma unroll
-	for (int k = 0; k < ARG_ITEMS; ++k) {
+	for (int k = 0; k < CLO_SEG_ITEMS; ++k) {
 		if ((closes >> k) & 1u) {
 			const bool full = (has_row >> nth) & 1u;
 			const unsigned i = LAST ? ~open.j() : open.j();
@@ -343,24 +280,24 @@ void clo_segarg_sweep_kernel(const TC* __restrict__ src, const arg_u64* __restri
 	if (val_out) clo_op_store<TV>(val_out + a0, na, tid, [&](unsigned i) { return s_val[i]; });
 }
 
-// ---- 4. carry scan: one group; tile t gets the state of the tiles before it, in place, ARG_CARRY_TRIP states per
-// trip (clo_segreduce_carry_kernel's walk); the next trip's states are requested before this trip's are combined ----
+// ---- 4. carry scan: one group; tile t gets the state of the tiles before it, in place. clo_seg_carry's walk
+// (clo_hip_seg_device.h) with this file's aggregate, held as three arrays of words ----
 template <int VS>
-__global__ __launch_bounds__(ARG_THREADS) __attribute__((amdgpu_waves_per_eu(1, 2)))   // one work-group: its registers hold two trips' states
+__global__ __launch_bounds__(CLO_SEG_THREADS) __attribute__((amdgpu_waves_per_eu(1, 2)))   // one work-group: its registers hold two trips' states
 void clo_segarg_carry_kernel(arg_tile_ws tw, unsigned tiles) {
 	typedef arg_agg<VS> A;
 	__shared__ arg_waves<A> s_waves;
 	const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
 	arg_state<A> running = arg_empty<A>();   // the state of everything before this trip (the same in every thread)
 	// (three arrays of words, not one of states: they stay in registers)
-	unsigned ahead_h[ARG_CARRY_ITEMS], ahead_j[ARG_CARRY_ITEMS];
-	arg_u64 ahead_x[ARG_CARRY_ITEMS];
+	unsigned ahead_h[CLO_SEG_CARRY_ITEMS], ahead_j[CLO_SEG_CARRY_ITEMS];
+	arg_u64 ahead_x[CLO_SEG_CARRY_ITEMS];
 	typedef unsigned vec4 __attribute__((ext_vector_type(4)));
 	typedef arg_u64 vec2 __attribute__((ext_vector_type(2)));
 	auto request = [&](unsigned first) {
-		if (first + ARG_CARRY_ITEMS <= tiles) {   // 16-byte loads: the arrays are 256-byte aligned, `first` a multiple of ARG_CARRY_ITEMS
+		if (first + CLO_SEG_CARRY_ITEMS <= tiles) {   // 16-byte loads: the arrays are 256-byte aligned, `first` a multiple of CLO_SEG_CARRY_ITEMS
 			#pragma unroll
-			for (int j = 0; j < ARG_CARRY_ITEMS; j += 4) {
+			for (int j = 0; j < CLO_SEG_CARRY_ITEMS; j += 4) {
 				const vec4 h = *reinterpret_cast<const vec4*>(tw.h + first + j);
 				ahead_h[j] = h.x; ahead_h[j + 1] = h.y; ahead_h[j + 2] = h.z; ahead_h[j + 3] = h.w;
 				vec4 jj = { ~0u, ~0u, ~0u, ~0u };
@@ -368,13 +305,13 @@ void clo_segarg_carry_kernel(arg_tile_ws tw, unsigned tiles) {
 				ahead_j[j] = jj.x; ahead_j[j + 1] = jj.y; ahead_j[j + 2] = jj.z; ahead_j[j + 3] = jj.w;
 			}
 			#pragma unroll
-			for (int j = 0; j < ARG_CARRY_ITEMS; j += 2) {
+			for (int j = 0; j < CLO_SEG_CARRY_ITEMS; j += 2) {
 				const vec2 x = *reinterpret_cast<const vec2*>(tw.ax + first + j);
 				ahead_x[j] = x.x; ahead_x[j + 1] = x.y;
 			}
 		} else {
 			#pragma unroll
-			for (int j = 0; j < ARG_CARRY_ITEMS; ++j) {
+			for (int j = 0; j < CLO_SEG_CARRY_ITEMS; ++j) {
 				const bool in = first + j < tiles;
 				ahead_h[j] = in ? tw.h[first + j] : 0u;
 				ahead_x[j] = in ? tw.ax[first + j] : ~0ull;
@@ -382,40 +319,40 @@ void clo_segarg_carry_kernel(arg_tile_ws tw, unsigned tiles) {
 			}
 		}
 	};
-	request(tid * ARG_CARRY_ITEMS);
-	for (unsigned chunk = 0; chunk < tiles; chunk += ARG_CARRY_TRIP) {
-		const unsigned t0 = chunk + tid * ARG_CARRY_ITEMS;
-		arg_state<A> st[ARG_CARRY_ITEMS];
+	request(tid * CLO_SEG_CARRY_ITEMS);
+	for (unsigned chunk = 0; chunk < tiles; chunk += CLO_SEG_CARRY_TRIP) {
+		const unsigned t0 = chunk + tid * CLO_SEG_CARRY_ITEMS;
+		arg_state<A> st[CLO_SEG_CARRY_ITEMS];
 		arg_state<A> mine = arg_empty<A>();
 		#pragma unroll
-		for (int j = 0; j < ARG_CARRY_ITEMS; ++j) {
+		for (int j = 0; j < CLO_SEG_CARRY_ITEMS; ++j) {
 			st[j].h = ahead_h[j];
 			st[j].a = A::words(ahead_x[j], ahead_j[j]);
 			mine = arg_combine<A>(mine, st[j]);
 		}
-		request(t0 + ARG_CARRY_TRIP);   // (this thread's own tiles of the next trip: nobody writes them before)
+		request(t0 + CLO_SEG_CARRY_TRIP);   // (this thread's own tiles of the next trip: nobody writes them before)
 		const arg_state<A> incl = arg_wave_scan<A>(mine);
 		if (lane == 63u) s_waves.put(wave, incl);
 		__syncthreads();
 		const typename arg_waves<A>::both waves = s_waves.get(wave, running);
 		arg_state<A> s = arg_combine<A>(waves.before, arg_wave_exclusive<A>(incl, lane));
-		arg_u64 out_x[ARG_CARRY_ITEMS];   // (tw.h is not needed again)
-		unsigned out_j[ARG_CARRY_ITEMS];
+		arg_u64 out_x[CLO_SEG_CARRY_ITEMS];   // (tw.h is not needed again)
+		unsigned out_j[CLO_SEG_CARRY_ITEMS];
 		#pragma unroll
-		for (int j = 0; j < ARG_CARRY_ITEMS; ++j) {
+		for (int j = 0; j < CLO_SEG_CARRY_ITEMS; ++j) {
 			out_x[j] = s.a.word(); out_j[j] = s.a.j();
 			s = arg_combine<A>(s, st[j]);
 		}
-		if (t0 + ARG_CARRY_ITEMS <= tiles) {
+		if (t0 + CLO_SEG_CARRY_ITEMS <= tiles) {
 			#pragma unroll
-			for (int j = 0; j < ARG_CARRY_ITEMS; j += 2) {
+			for (int j = 0; j < CLO_SEG_CARRY_ITEMS; j += 2) {
 				vec2 x;
 				x.x = out_x[j]; x.y = out_x[j + 1];
 				*reinterpret_cast<vec2*>(tw.ax + t0 + j) = x;
 			}
 			if (VS == 8) {
 				#pragma unroll
-				for (int j = 0; j < ARG_CARRY_ITEMS; j += 4) {
+				for (int j = 0; j < CLO_SEG_CARRY_ITEMS; j += 4) {
 					vec4 jj;
 					jj.x = out_j[j]; jj.y = out_j[j + 1]; jj.z = out_j[j + 2]; jj.w = out_j[j + 3];
 					*reinterpret_cast<vec4*>(tw.aj + t0 + j) = jj;
@@ -423,7 +360,7 @@ void clo_segarg_carry_kernel(arg_tile_ws tw, unsigned tiles) {
 			}
 		} else {
 			#pragma unroll
-			for (int j = 0; j < ARG_CARRY_ITEMS; ++j) {
+			for (int j = 0; j < CLO_SEG_CARRY_ITEMS; ++j) {
 				if (t0 + j < tiles) {
 					tw.ax[t0 + j] = out_x[j];
 					if (VS == 8) tw.aj[t0 + j] = out_j[j];
@@ -438,81 +375,80 @@ void clo_segarg_carry_kernel(arg_tile_ws tw, unsigned tiles) {
 // ---- 5. fix-up: the first segment that closes in tile t = (the carry into the tile) best (what the tile holds of it);
 // whether it has a row at all comes from its clipped ends. (A segment closes in exactly one tile, so no two threads meet.) ----
 template <typename TC, bool OFFSETS, int VS, bool LAST>
-__global__ __launch_bounds__(ARG_THREADS)
+__global__ __launch_bounds__(CLO_SEG_THREADS)
 void clo_segarg_fixup_kernel(const TC* __restrict__ src, const arg_u64* __restrict__ ends, const arg_u64* __restrict__ num_in, unsigned m_h, unsigned n,
 	arg_tile_ws tw, unsigned tiles, unsigned* __restrict__ idx_out, typename arg_agg<VS>::TV* __restrict__ val_out, arg_key key) {
 	typedef arg_agg<VS> A;
 	typedef typename A::TV TV;
-	const unsigned t = blockIdx.x * ARG_THREADS + threadIdx.x;
+	const unsigned t = blockIdx.x * CLO_SEG_THREADS + threadIdx.x;
 	if (t >= tiles) return;
 	const unsigned r = tw.first[t];
 	if (r >= clo_op_segments(num_in, m_h)) return;   // ARG_NONE, or not a segment
 	const clo_op_ends<TC, OFFSETS> e = clo_op_ends_make<TC, OFFSETS>(src, ends);
-	const arg_u64 from = r > 0u ? arg_min64(e.at(r - 1u), n) : 0ull, to = arg_min64(e.at(r), n);
+	const arg_u64 from = r > 0u ? clo_op_min64(e.at(r - 1u), n) : 0ull, to = clo_op_min64(e.at(r), n);
 	const A best = arg_best<A>(A::words(tw.ax[t], tw.aj[t]), A::words(tw.px[t], tw.pj[t]));   // the carry lies to the left
 	const bool full = to > from;
 	idx_out[r] = full ? (LAST ? ~best.j() : best.j()) : ARG_NONE;
 	if (val_out) val_out[r] = arg_value_of<TV>(full ? best.key() : (TV) ~(TV) 0, key);
 }
 
-struct arg_args {
+// The workspace: the ends of the counts form, the tile boundaries' splits, the tiles' four 32-bit and two 64-bit words,
+// the sums of the ends' scan. Laid out from `base`, or only measured where that is null; returns the size.
+struct arg_ws { arg_u64* ends; unsigned* split; arg_tile_ws tw; arg_u64* tsum; };
+
+inline size_t arg_layout(arg_ws& w, char* base, size_t numel_seg, size_t numel) {
+	const size_t tiles = clo_seg_tiles(numel_seg, numel);
+	size_t at = 0;
+	w.ends = clo_op_ws_take<arg_u64>(base, at, numel_seg);
+	w.split = clo_op_ws_take<unsigned>(base, at, tiles + 1);
+	w.tw.h = clo_op_ws_take<unsigned>(base, at, tiles);
+	w.tw.first = clo_op_ws_take<unsigned>(base, at, tiles);
+	w.tw.aj = clo_op_ws_take<unsigned>(base, at, tiles);
+	w.tw.pj = clo_op_ws_take<unsigned>(base, at, tiles);
+	w.tw.ax = clo_op_ws_take<arg_u64>(base, at, tiles);
+	w.tw.px = clo_op_ws_take<arg_u64>(base, at, tiles);
+	w.tsum = clo_op_ws_take<arg_u64>(base, at, clo_op_ends_tiles(numel_seg) + 1);
+	return at;
+}
+
+struct arg_args : arg_ws {
 	const void* src; const arg_u64* num_in; const void* vin; unsigned* idx; void* val; arg_u64* num_out;
-	unsigned m_h, n; arg_key key;
-	arg_u64* ends; unsigned* split; arg_tile_ws tw; arg_u64* tsum; hipStream_t s;
+	unsigned m_h, n; arg_key key; hipStream_t s;
 };
 
-template <typename TC>
-int arg_ends_launch(const arg_args& a) {
-	const unsigned tiles = (unsigned) clo_op_ends_tiles(a.m_h);
-	const int vec_ok = clo_op_vec_ok<TC>(a.src);
-	{
-		clo_timing_scope timing("segarg_sums", a.s);
-		hipLaunchKernelGGL((clo_segarg_sums_kernel<TC>), dim3(tiles), dim3(ARG_THREADS), 0, a.s, (const TC*) a.src, a.num_in, a.m_h, vec_ok, a.tsum);
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return (int) e;
-	}
-	{
-		clo_timing_scope timing("segarg_sums_scan", a.s);
-		hipLaunchKernelGGL(clo_segarg_sums_scan_kernel, dim3(1), dim3(ARG_THREADS), 0, a.s, a.tsum, tiles);
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return (int) e;
-	}
-	clo_timing_scope timing("segarg_ends", a.s);
-	hipLaunchKernelGGL((clo_segarg_ends_kernel<TC>), dim3(tiles), dim3(ARG_THREADS), 0, a.s, (const TC*) a.src, a.num_in, a.m_h, vec_ok,
-		(const arg_u64*) a.tsum, a.ends);
-	return (int) hipGetLastError();
-}
+constexpr const char* ARG_ENDS_LABELS[3] = { "segarg_sums", "segarg_sums_scan", "segarg_ends" };
 
 template <typename TC, bool OFFSETS, int VS, bool LAST>
 int arg_launch(const arg_args& a) {
 	typedef typename arg_agg<VS>::TV TV;
 	if constexpr (!OFFSETS) {
-		const int st = arg_ends_launch<TC>(a);
+		const int st = clo_op_ends_launch<TC>(clo_segarg_sums_kernel<TC>, clo_segarg_sums_scan_kernel, clo_segarg_ends_kernel<TC>, ARG_ENDS_LABELS,
+			a.src, a.num_in, a.m_h, a.tsum, a.ends, a.s);
 		if (st != 0) return st;
 	}
-	const unsigned tiles = (unsigned) arg_tiles(a.m_h, a.n);   // >= 1: m_h > 0
+	const unsigned tiles = (unsigned) clo_seg_tiles(a.m_h, a.n);   // >= 1: m_h > 0
 	{
 		clo_timing_scope timing("segarg_partition", a.s);
-		hipLaunchKernelGGL((clo_segarg_partition_kernel<TC, OFFSETS>), dim3(tiles / ARG_THREADS + 1u), dim3(ARG_THREADS), 0, a.s,
+		hipLaunchKernelGGL((clo_segarg_partition_kernel<TC, OFFSETS>), dim3(tiles / CLO_SEG_THREADS + 1u), dim3(CLO_SEG_THREADS), 0, a.s,
 			(const TC*) a.src, (const arg_u64*) a.ends, a.num_in, a.m_h, a.n, tiles, a.split, a.num_out);
 		const hipError_t e = hipGetLastError();
 		if (e != hipSuccess) return (int) e;
 	}
 	{
 		clo_timing_scope timing("segarg_sweep", a.s);
-		hipLaunchKernelGGL((clo_segarg_sweep_kernel<TC, OFFSETS, VS, LAST>), dim3(tiles), dim3(ARG_THREADS), 0, a.s,
+		hipLaunchKernelGGL((clo_segarg_sweep_kernel<TC, OFFSETS, VS, LAST>), dim3(tiles), dim3(CLO_SEG_THREADS), 0, a.s,
 			(const TC*) a.src, (const arg_u64*) a.ends, a.num_in, a.m_h, a.n, (const unsigned*) a.split, (const TV*) a.vin, a.idx, (TV*) a.val, a.key, a.tw);
 		const hipError_t e = hipGetLastError();
 		if (e != hipSuccess) return (int) e;
 	}
 	{
 		clo_timing_scope timing("segarg_carry", a.s);
-		hipLaunchKernelGGL((clo_segarg_carry_kernel<VS>), dim3(1), dim3(ARG_THREADS), 0, a.s, a.tw, tiles);
+		hipLaunchKernelGGL((clo_segarg_carry_kernel<VS>), dim3(1), dim3(CLO_SEG_THREADS), 0, a.s, a.tw, tiles);
 		const hipError_t e = hipGetLastError();
 		if (e != hipSuccess) return (int) e;
 	}
 	clo_timing_scope timing("segarg_fixup", a.s);
-	hipLaunchKernelGGL((clo_segarg_fixup_kernel<TC, OFFSETS, VS, LAST>), dim3((tiles + ARG_THREADS - 1u) / ARG_THREADS), dim3(ARG_THREADS), 0, a.s,
+	hipLaunchKernelGGL((clo_segarg_fixup_kernel<TC, OFFSETS, VS, LAST>), dim3((tiles + CLO_SEG_THREADS - 1u) / CLO_SEG_THREADS), dim3(CLO_SEG_THREADS), 0, a.s,
 		(const TC*) a.src, (const arg_u64*) a.ends, a.num_in, a.m_h, a.n, a.tw, tiles, a.idx, (TV*) a.val, a.key);
 	return (int) hipGetLastError();
 }
@@ -536,16 +472,14 @@ inline int arg_size(int t) { return t == 6 || t == 7 || t == 10 ? 8 : 4; }
 
 extern "C" {
 
-size_t clo_hip_segarg_tile(int value_size) { return value_size == 4 || value_size == 8 ? ARG_TILE : 0; }
+size_t clo_hip_segarg_tile(int value_size) { return value_size == 4 || value_size == 8 ? CLO_SEG_TILE : 0; }
 
-size_t clo_hip_segarg_carry_tiles(void) { return ARG_CARRY_TRIP; }
+size_t clo_hip_segarg_carry_tiles(void) { return CLO_SEG_CARRY_TRIP; }
 
 size_t clo_hip_segarg_workspace_bytes(size_t numel_seg, size_t numel) {
 	if (numel_seg == 0 && numel == 0) return 0;
-	const size_t tiles = arg_tiles(numel_seg, numel);
-	// the ends of the counts form, the tile boundaries' splits, the tiles' four 32-bit and two 64-bit words, the sums of the ends' scan
-	return clo_op_ws_align(numel_seg * sizeof(arg_u64)) + clo_op_ws_align((tiles + 1) * sizeof(unsigned)) + 4 * clo_op_ws_align(tiles * sizeof(unsigned))
-		+ 2 * clo_op_ws_align(tiles * sizeof(arg_u64)) + clo_op_ws_align((clo_op_ends_tiles(numel_seg) + 1) * sizeof(arg_u64));
+	arg_ws w;
+	return arg_layout(w, nullptr, numel_seg, numel);
 }
 
 int clo_hip_segarg(int op, int tie, int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* values_in,
@@ -577,22 +511,7 @@ int clo_hip_segarg(int op, int tie, int form, const void* counts_or_offsets, int
 	a.m_h = (unsigned) numel_seg; a.n = (unsigned) numel; a.s = (hipStream_t) stream;
 	a.key.kx = clo_keyx_make(kind, 0, (int) (8 * vs));
 	a.key.cmpl = op == CLO_HIP_SEGARG_ARGMAX ? ~0ull : 0ull;
-	const size_t tiles = arg_tiles(numel_seg, numel);
-	char* ws = (char*) workspace;
-	a.ends = (arg_u64*) ws;
-	ws += clo_op_ws_align(numel_seg * sizeof(arg_u64));
-	a.split = (unsigned*) ws;
-	ws += clo_op_ws_align((tiles + 1) * sizeof(unsigned));
-	unsigned** const words[4] = { &a.tw.h, &a.tw.first, &a.tw.aj, &a.tw.pj };
-	for (int k = 0; k < 4; ++k) {
-		*words[k] = (unsigned*) ws;
-		ws += clo_op_ws_align(tiles * sizeof(unsigned));
-	}
-	a.tw.ax = (arg_u64*) ws;
-	ws += clo_op_ws_align(tiles * sizeof(arg_u64));
-	a.tw.px = (arg_u64*) ws;
-	ws += clo_op_ws_align(tiles * sizeof(arg_u64));
-	a.tsum = (arg_u64*) ws;
+	arg_layout(a, (char*) workspace, numel_seg, numel);
 	return count_size == 8 ? arg_dispatch<uint64_t>(a, form, (int) vs, tie) : arg_dispatch<uint32_t>(a, form, (int) vs, tie);
 }
 

@@ -4,7 +4,7 @@
 // order clo_keyx gives, equal keys in their input order, the values (or the global row index) moving with them.
 //
 // A segmented merge sort over fixed tiles of T = 2048 rows. No launch waits for another work-group or uses an atomic:
-//   ENDS    the counts form only: the numel_seg inclusive ends as uint64 in the workspace (clo_hip_op_device.h).
+//   ENDS    the counts form only: the numel_seg inclusive ends as uint64 in the workspace (clo_hip_seg_device.h).
 //   HEADS   the flags (one byte per row, zeroed by a memset before) get a 1 at row s_r of every non-empty segment that
 //           starts below n: one thread per segment, so that empty segments cost one thread each and nothing later. The
 //           starts of non-empty segments are distinct, no two threads write one byte. Thread 0 writes num_out.
@@ -34,7 +34,7 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
-#include "clo_hip_op_device.h"
+#include "clo_hip_seg_device.h"
 
 namespace {
 
@@ -42,7 +42,7 @@ typedef clo_op_u64 ss_u64;
 
 constexpr int SS_THREADS = 256;
 constexpr int SS_WAVES = SS_THREADS / 64;
-static_assert(SS_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS");
+static_assert(SS_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS, and clo_op_ends_launch launches groups of it");
 constexpr int SS_ITEMS = 8;                              // consecutive rows of a lane: one 8-byte load of flags
 constexpr unsigned SS_TILE = SS_THREADS * SS_ITEMS;      // T = 2048 rows, for every type
 static_assert((SS_TILE & (SS_TILE - 1u)) == 0u && SS_TILE < 32768u, "a power of two; rank and row take 16 bits each");
@@ -50,10 +50,7 @@ static_assert((SS_TILE & (SS_TILE - 1u)) == 0u && SS_TILE < 32768u, "a power of 
 inline size_t ss_tiles(size_t numel) { return (numel + SS_TILE - 1) / SS_TILE; }
 inline int ss_passes(size_t tiles) { int p = 0; while (((size_t) 1 << p) < tiles) ++p; return p; }
 
-__device__ __forceinline__ ss_u64 ss_min64(ss_u64 a, ss_u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ ss_u64 ss_max64(ss_u64 a, ss_u64 b) { return a > b ? a : b; }
-
-// ---- 1. the ends of the counts form: the three launches of clo_hip_op_device.h ----
+// ---- 1. the ends of the counts form: the three launches of clo_hip_seg_device.h ----
 
 template <typename TC>
 __global__ __launch_bounds__(SS_THREADS)
@@ -114,8 +111,8 @@ __device__ __forceinline__ ss_seg ss_find(const clo_op_ends<TC, OFFSETS>& e, uns
 	ss_seg g;
 	g.s = 0u; g.e = 0u; g.mask = 0u;
 	if (lo < m) {
-		const ss_u64 ee = ss_min64(e.at(lo), n);
-		const ss_u64 s = lo > 0u ? ss_min64(e.at(lo - 1u), ee) : 0ull;
+		const ss_u64 ee = clo_op_min64(e.at(lo), n);
+		const ss_u64 s = lo > 0u ? clo_op_min64(e.at(lo - 1u), ee) : 0ull;
 		g.s = (unsigned) s; g.e = (unsigned) ee;
 		g.mask = ss_moves(g.s, g.e);
 	}
@@ -135,10 +132,10 @@ __device__ __forceinline__ ss_tile ss_tile_of(const TC* __restrict__ src, const 
 	ss_tile t;
 	const unsigned m = clo_op_segments(num_in, m_h);
 	const clo_op_ends<TC, OFFSETS> e = clo_op_ends_make<TC, OFFSETS>(src, ends);
-	const ss_u64 lim = ss_min64(m > 0u ? e.at(m - 1u) : 0ull, n);
+	const ss_u64 lim = clo_op_min64(m > 0u ? e.at(m - 1u) : 0ull, n);
 	const ss_u64 t0 = (ss_u64) blockIdx.x * SS_TILE;
-	t.tile0 = (unsigned) ss_min64(t0, n);
-	t.cnt = t0 < lim ? (unsigned) ss_min64(SS_TILE, lim - t0) : 0u;
+	t.tile0 = (unsigned) clo_op_min64(t0, n);
+	t.cnt = t0 < lim ? (unsigned) clo_op_min64(SS_TILE, lim - t0) : 0u;
 	t.A.s = t.A.e = t.A.mask = 0u;
 	t.B = t.A;
 	if (t.cnt > 0u && !info) {
@@ -330,7 +327,7 @@ __device__ __forceinline__ void ss_merge_part(const ss_seg& g, const ss_tile& t,
 		return;
 	}
 	// left part [first, mid), right part [mid, last), both inside [0, n): mid < e <= n
-	const unsigned first = (unsigned) ss_max64(g.s, lo), um = (unsigned) mid, last = (unsigned) ss_min64(g.e, hi);
+	const unsigned first = (unsigned) clo_op_max64(g.s, lo), um = (unsigned) mid, last = (unsigned) clo_op_min64(g.e, hi);
 	const unsigned na = um - first, nb = last - um;
 	const unsigned d0 = o0 - first, d1 = o1 - first;   // o0 >= first, o1 <= last
 	if (tid < 2u) s_split[tid] = clo_op_path<TK, true>(ksrc + first, ksrc + um, na, nb, tid == 0u ? d0 : d1, kx);
@@ -389,31 +386,14 @@ struct ss_args {
 
 #define SS_CHECK_LAUNCH() do { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int) e_; } while (0)
 
-template <typename TC>
-int ss_ends_launch(const ss_args& a) {
-	const unsigned tiles = (unsigned) clo_op_ends_tiles(a.m_h);
-	const int vec_ok = clo_op_vec_ok<TC>(a.src);
-	{
-		clo_timing_scope timing("segsort_sums", a.s);
-		hipLaunchKernelGGL((clo_segsort_sums_kernel<TC>), dim3(tiles), dim3(SS_THREADS), 0, a.s, (const TC*) a.src, a.num_in, a.m_h, vec_ok, a.tsum);
-		SS_CHECK_LAUNCH();
-	}
-	{
-		clo_timing_scope timing("segsort_sums_scan", a.s);
-		hipLaunchKernelGGL(clo_segsort_sums_scan_kernel, dim3(1), dim3(SS_THREADS), 0, a.s, a.tsum, tiles);
-		SS_CHECK_LAUNCH();
-	}
-	clo_timing_scope timing("segsort_ends", a.s);
-	hipLaunchKernelGGL((clo_segsort_ends_kernel<TC>), dim3(tiles), dim3(SS_THREADS), 0, a.s, (const TC*) a.src, a.num_in, a.m_h, vec_ok,
-		(const ss_u64*) a.tsum, a.ends);
-	return (int) hipGetLastError();
-}
+constexpr const char* SS_ENDS_LABELS[3] = { "segsort_sums", "segsort_sums_scan", "segsort_ends" };
 
 template <typename TK, typename TC, bool OFFSETS, int MODE>
 int ss_launch(const ss_args& a) {
 	typedef typename clo_op_val<MODE>::T TV;
 	if constexpr (!OFFSETS) {
-		const int st = ss_ends_launch<TC>(a);
+		const int st = clo_op_ends_launch<TC>(clo_segsort_sums_kernel<TC>, clo_segsort_sums_scan_kernel, clo_segsort_ends_kernel<TC>, SS_ENDS_LABELS,
+			a.src, a.num_in, a.m_h, a.tsum, a.ends, a.s);
 		if (st != 0) return st;
 	}
 	const unsigned tiles = (unsigned) ss_tiles(a.n);

@@ -1,7 +1,7 @@
 """What CloSegScan's kernels (cl_ops_amd/csrc/hip/clo_hip_segscan.hip) do one level below the tile,
 computed with numpy from segscan_model.merge_steps alone: nothing here calls the library. The rules are the kernel's,
 restated:
-  the tile        sscan_tile_range: tile t holds the merge steps [d0, d1) = [min(t T, m + n), min(t T + T, m + n)), cnt of
+  the tile        clo_seg_tile_range: tile t holds the merge steps [d0, d1) = [min(t T, m + n), min(t T + T, m + n)), cnt of
                   them; na of them close the ends [a0, a0 + na), nb = cnt - na take the rows [b0, b0 + nb), b0 = d0 - a0.
                   There are ceil((numel_seg + n) / T) tiles, whatever num_in leaves of the segments. SWEEP stores the
                   tile's rows below ct = min(total, n): nstore = max(min(b0 + nb, ct), b0) - b0.
@@ -16,14 +16,14 @@ restated:
   SWEEP, a wave   64 lanes, 64 * 17 steps; its state's head count is the number of its closes.
   CARRY           thread i of 256 holds the states of the tiles [16 i, 16 i + 16) of a trip of 4096; it loads them with
                   16-byte loads where 16 i + 16 <= tiles and one by one otherwise.
-The lane items and carry items are the kernel's SCAN_ITEMS and SCAN_CARRY_ITEMS; T comes from the library's getter and is
+The lane items and carry items are the kernel's CLO_SEG_ITEMS and CLO_SEG_CARRY_ITEMS; T comes from the library's getter and is
 passed in."""
 import numpy as np
 
 from segscan_model import merge_steps
 
-ITEMS = 17         # SCAN_ITEMS: merge steps per lane
-CARRY_ITEMS = 16   # SCAN_CARRY_ITEMS: tile states per thread of the carry scan
+ITEMS = 17         # CLO_SEG_ITEMS: merge steps per lane
+CARRY_ITEMS = 16   # CLO_SEG_CARRY_ITEMS: tile states per thread of the carry scan
 WAVE = 64
 
 
@@ -75,7 +75,7 @@ def lanes(form, counts_or_offsets, n, T, num_in=None, value_size=4, align=0, ite
         e = np.clip(ends[a0:a0 + na] - b0, 0, nb)                              # s_end
         d = np.minimum(lane * items, cnt)
         a = np.searchsorted(e + np.arange(na), d, "left")                      # the halving: ends with e_k <= d - 1 - k
-        a[threads] = na                                                        # s_start[SCAN_THREADS]
+        a[threads] = na                                                        # s_start[CLO_SEG_THREADS]
         a, d, nxt = a[:threads], d[:threads], a[1:]
         b = d - a
         steps = np.minimum(items, cnt - d)

@@ -179,7 +179,7 @@ def test_merge_lengths_around_the_tile_edges(dev, T):
             assert got == n
 
 
-# clo_hip_segreduce.hip: SEG_CARRY_TRIP = SEG_THREADS * SEG_CARRY_ITEMS, the tile states the one work-group of the carry
+# clo_hip_seg_device.h: CLO_SEG_CARRY_TRIP = CLO_SEG_THREADS * CLO_SEG_CARRY_ITEMS, the tile states the one work-group of the carry
 # scan takes per trip (4096 today; there is no getter). The cases below hold two trips and 108 tiles: three trips, and
 # still a second one if a trip were doubled.
 CARRY_TRIP = 4096

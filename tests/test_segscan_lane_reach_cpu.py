@@ -27,7 +27,7 @@ def models():
 
 def test_the_constants_are_the_librarys():
     assert T == clo.segscan_tile(4, 8) == clo.segscan_tile(8, 8) and T % ITEMS == 0
-    assert T // ITEMS == 256 == 4 * WAVE                                        # SCAN_THREADS, four waves
+    assert T // ITEMS == 256 == 4 * WAVE                                        # CLO_SEG_THREADS, four waves
     assert clo.segreduce_tile(4, 4) == T                                        # the carry layouts of the other files are in these steps
     assert CARRY_ITEMS == 16 and 256 * CARRY_ITEMS == 4096                      # a trip of the carry scan
 
