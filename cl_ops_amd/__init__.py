@@ -1,4 +1,4 @@
-"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/selection/top-k/expansion/segmented-reduction/segmented-sort/segmented-scan/bucket-partition/segmented-arg-min-max primitives and device RNGs behind the cl_ops C API.
+"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/join/selection/top-k/expansion/segmented-reduction/segmented-sort/segmented-scan/bucket-partition/segmented-arg-min-max primitives and device RNGs behind the cl_ops C API.
 
 The product is cl_ops_amd/lib/libcl_ops_hip.so (C-ABI, see include/): host
 drivers in C (cl_ops_amd/csrc) + hand-written HIP kernels for gfx950
@@ -16,6 +16,7 @@ from .histogram import Histogram, histogram_tile, histogram_lds_bins  # noqa: F4
 from .merge import Merge, merge_tile  # noqa: F401
 from .search import Search, search_tile, search_lds_keys, search_pivots  # noqa: F401
 from .setop import SetOp, setop_tile  # noqa: F401
+from .join import Join, join_tile, join_out_tile, JOIN_KINDS, JOIN_NONE  # noqa: F401
 from .select import Select, select_tile  # noqa: F401
 from .expand import Expand, expand_tile, expand_lds_segments, EXPAND_FORMS  # noqa: F401
 from .segreduce import SegReduce, segreduce_tile, SEGREDUCE_OPS, SEGREDUCE_FORMS  # noqa: F401
@@ -29,7 +30,7 @@ __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profi
            "ShardTransport", "ShardSort", "Rng", "rng_names", "ReduceByKey", "reduce_by_key_tile",
            "ScanByKey", "scan_by_key_tile", "Histogram", "histogram_tile", "histogram_lds_bins",
            "Merge", "merge_tile", "Search", "search_tile", "search_lds_keys", "search_pivots",
-           "SetOp", "setop_tile", "Select", "select_tile",
+           "SetOp", "setop_tile", "Join", "join_tile", "join_out_tile", "JOIN_KINDS", "JOIN_NONE", "Select", "select_tile",
            "TopK", "topk_tile", "topk_sweep_groups", "topk_sorted_max", "TOPK_WHICH", "TOPK_ORDERS",
            "Expand", "expand_tile", "expand_lds_segments", "EXPAND_FORMS",
            "SegReduce", "segreduce_tile", "SEGREDUCE_OPS", "SEGREDUCE_FORMS",

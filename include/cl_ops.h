@@ -24,6 +24,7 @@
 #include "clo_segscan.h"
 #include "clo_bucket.h"
 #include "clo_segarg.h"
+#include "clo_join.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

@@ -325,6 +325,38 @@ int clo_hip_setop(int op, const void* keys_a, const void* values_a, size_t numel
 	void* keys_out, void* values_out, uint64_t* num_out, int key_size, int key_kind,
 	int value_size, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- equi-join (new functionality: CloJoin, include/clo_join.h) ----
+ * The inner, left, right or full outer join of keys_a[0, numel_a) and keys_b[0, numel_b), each ascending (keys and
+ * key_kind as for clo_hip_merge), as rows (idx_a, idx_b, key) in ascending key order; a side without a partner holds
+ * CLO_HIP_JOIN_NONE (include/clo_join.h has the rows and their order). *num_out = K, the rows of the whole join, a
+ * uint64_t of device memory, 8-byte aligned: K may exceed both `capacity` and 2^32. Rows [0, min(K, capacity)) are
+ * written to those of idx_a_out, idx_b_out and keys_out that are not NULL, each holding `capacity` (< 2^32) rows;
+ * nothing is written at an index >= min(K, capacity). All three NULL and capacity 0: the count form, which writes
+ * num_out alone. numel_a + numel_b < 2^32.
+ *
+ * Status: CLO_HIP_EARGS (a kind outside 0..3, key_kind outside 0..2, NULL keys of a non-empty input, num_out NULL or
+ * misaligned, capacity > 0 with all outputs NULL, a pointer not aligned to its element, numel_a + numel_b or capacity
+ * >= 2^32, the workspace NULL or not CLO_HIP_WORKSPACE_ALIGN-aligned while numel_a + numel_b > 0), CLO_HIP_EUNSUPPORTED
+ * (a key_size other than 1, 2, 4, 8; key_kind 2 with key_size 1), CLO_HIP_EWORKSPACE.
+ * Five launches, three in the count form (the merged tiles' split points; every merged element's rows and the tiles'
+ * totals; one work-group that turns the totals into offsets and writes num_out; the output tiles' first emitters; the
+ * write, one work-group per clo_hip_join_out_tile() rows of the RESULT); no work-group waits for another and there are
+ * no global atomics; asynchronous on `stream`; nothing is allocated and the host never waits, so the call can be
+ * captured into a graph. clo_hip_join_tile: the merged elements per tile, 0 for sizes not built.
+ * clo_hip_join_workspace_bytes is monotone in numel_a and numel_b, 0 for n = 0 or an unknown kind. */
+#define CLO_HIP_JOIN_INNER 0
+#define CLO_HIP_JOIN_LEFT  1
+#define CLO_HIP_JOIN_RIGHT 2
+#define CLO_HIP_JOIN_FULL  3
+#define CLO_HIP_JOIN_NONE  0xFFFFFFFFu
+size_t clo_hip_join_tile(int key_size);
+size_t clo_hip_join_out_tile(void);
+size_t clo_hip_join_workspace_bytes(int kind, size_t numel_a, size_t numel_b);
+int clo_hip_join(int kind, const void* keys_a, size_t numel_a, const void* keys_b, size_t numel_b,
+	uint32_t* idx_a_out, uint32_t* idx_b_out, void* keys_out, size_t capacity,
+	uint64_t* num_out, int key_size, int key_kind,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- selection and partition (new functionality: CloSelect, include/clo_select.h) ----
  * Element i of keys_in[0, numel) is KEPT iff flags[i] != 0 (pred CLO_HIP_SELECT_FLAGGED: flags_or_threshold points to
  * numel bytes, the keys are opaque) or iff keys_in[i] <pred> threshold in clo_hip_merge's order of key_kind (0 unsigned,
