@@ -34,18 +34,16 @@
 
 #include "clo_hip.h"
 #include "clo_hip_internal.h"
-#include "clo_hip_seg_device.h"
+#include "clo_hip_tile_sort_device.h"
 
 namespace {
 
 typedef clo_op_u64 ss_u64;
 
-constexpr int SS_THREADS = 256;
-constexpr int SS_WAVES = SS_THREADS / 64;
-static_assert(SS_THREADS == CLO_OP_THREADS, "the shared helpers stride by CLO_OP_THREADS, and clo_op_ends_launch launches groups of it");
-constexpr int SS_ITEMS = 8;                              // consecutive rows of a lane: one 8-byte load of flags
-constexpr unsigned SS_TILE = SS_THREADS * SS_ITEMS;      // T = 2048 rows, for every type
-static_assert((SS_TILE & (SS_TILE - 1u)) == 0u && SS_TILE < 32768u, "a power of two; rank and row take 16 bits each");
+constexpr int SS_THREADS = CLO_TS_THREADS;
+constexpr int SS_WAVES = CLO_TS_WAVES;
+constexpr int SS_ITEMS = CLO_TS_ITEMS;
+constexpr unsigned SS_TILE = CLO_TS_TILE;                // T = 2048 rows, for every type
 
 inline size_t ss_tiles(size_t numel) { return (numel + SS_TILE - 1) / SS_TILE; }
 inline int ss_passes(size_t tiles) { int p = 0; while (((size_t) 1 << p) < tiles) ++p; return p; }
@@ -149,45 +147,7 @@ __device__ __forceinline__ ss_tile ss_tile_of(const TC* __restrict__ src, const 
 	return t;
 }
 
-// ---- 3. tile sort ----
-// Where element i of the tile lies in LDS: inside every aligned group of eight the place is i ^ (group & 7), so that the
-// lanes' reads of their own eight consecutive elements (64 or 96 bytes apart) spread over the banks, and a step of
-// distance >= 8, whose lanes read consecutive elements, stays spread.
-__device__ __forceinline__ unsigned ss_at(unsigned i) { return i ^ ((i >> 3) & 7u); }
-
-// What the network sorts. Keys of up to 4 bytes: k = rank << 48 | order key << 16 | row, tag unused. 8-byte keys: k the
-// order key, tag = rank << 16 | row. The padding (all ones) sorts behind every row.
-struct ss_item { ss_u64 k; unsigned tag; };
-
-template <bool WIDE>
-__device__ __forceinline__ bool ss_less(const ss_item& a, const ss_item& b) {
-	if constexpr (!WIDE) return a.k < b.k;
-	else {
-		const unsigned sa = a.tag >> 16, sb = b.tag >> 16;
-		return sa != sb ? sa < sb : a.k != b.k ? a.k < b.k : a.tag < b.tag;
-	}
-}
-
-template <bool WIDE>
-__device__ __forceinline__ void ss_cx(ss_item& a, ss_item& b, bool up) {
-	if (ss_less<WIDE>(b, a) == up) { const ss_item t = a; a = b; b = t; }
-}
-
-// the steps of distance J < SS_ITEMS of stage `size`, on the lane's own rows [base, base + SS_ITEMS)
-template <bool WIDE, int J>
-__device__ __forceinline__ void ss_reg_step(ss_item (&v)[SS_ITEMS], unsigned base, unsigned size) {
-	#pragma unroll
-	for (int c = 0; c < SS_ITEMS; ++c)
-		if ((c & J) == 0) ss_cx<WIDE>(v[c], v[c | J], ((base + (unsigned) c) & size) == 0u);
-}
-
-template <bool WIDE>
-__device__ __forceinline__ void ss_reg_steps(ss_item (&v)[SS_ITEMS], unsigned base, unsigned size) {
-	if (size >= 8u) ss_reg_step<WIDE, 4>(v, base, size);
-	if (size >= 4u) ss_reg_step<WIDE, 2>(v, base, size);
-	ss_reg_step<WIDE, 1>(v, base, size);
-}
-
+// ---- 3. tile sort: the network, its item and the LDS layout are clo_hip_tile_sort_device.h's ----
 template <typename TK, typename TC, bool OFFSETS, int MODE>
 __global__ __launch_bounds__(SS_THREADS)
 void clo_segsort_tile_kernel(const TC* __restrict__ src, const ss_u64* __restrict__ ends, const ss_u64* __restrict__ num_in, unsigned m_h, unsigned n,
@@ -225,7 +185,7 @@ void clo_segsort_tile_kernel(const TC* __restrict__ src, const ss_u64* __restric
 		#pragma unroll
 		for (int c = 0; c < CLO_OP_VEC; ++c) { raw[c] = a[c]; raw[c + CLO_OP_VEC] = b[c]; }
 	}
-	ss_item v[SS_ITEMS];
+	clo_ts_item v[SS_ITEMS];
 	#pragma unroll
 	for (int c = 0; c < SS_ITEMS; ++c) {
 		const unsigned row = base + (unsigned) c;
@@ -238,44 +198,7 @@ void clo_segsort_tile_kernel(const TC* __restrict__ src, const ss_u64* __restric
 			v[c].k = ~0ull; v[c].tag = 0xffffffffu;
 		}
 	}
-	ss_reg_steps<WIDE>(v, base, 2u);
-	ss_reg_steps<WIDE>(v, base, 4u);
-	ss_reg_steps<WIDE>(v, base, 8u);
-	#pragma unroll
-	for (int c = 0; c < SS_ITEMS; ++c) {
-		s_k[ss_at(base + c)] = v[c].k;
-		if constexpr (WIDE) s_tag[ss_at(base + c)] = v[c].tag;
-	}
-	__syncthreads();
-	for (unsigned size = 16u; size <= SS_TILE; size <<= 1) {
-		for (unsigned j = size >> 1; j >= (unsigned) SS_ITEMS; j >>= 1) {
-			#pragma unroll
-			for (unsigned q = 0; q < SS_TILE / 2u / SS_THREADS; ++q) {
-				const unsigned pr = tid + q * SS_THREADS;
-				const unsigned ea = ((pr & ~(j - 1u)) << 1) | (pr & (j - 1u)), ia = ss_at(ea), ib = ss_at(ea | j);
-				ss_item a, b;
-				a.k = s_k[ia]; b.k = s_k[ib];
-				if constexpr (WIDE) { a.tag = s_tag[ia]; b.tag = s_tag[ib]; } else { a.tag = 0u; b.tag = 0u; }
-				if (ss_less<WIDE>(b, a) == ((ea & size) == 0u)) {
-					s_k[ia] = b.k; s_k[ib] = a.k;
-					if constexpr (WIDE) { s_tag[ia] = b.tag; s_tag[ib] = a.tag; }
-				}
-			}
-			__syncthreads();
-		}
-		#pragma unroll
-		for (int c = 0; c < SS_ITEMS; ++c) {
-			v[c].k = s_k[ss_at(base + c)];
-			if constexpr (WIDE) v[c].tag = s_tag[ss_at(base + c)]; else v[c].tag = 0u;
-		}
-		ss_reg_steps<WIDE>(v, base, size);
-		#pragma unroll
-		for (int c = 0; c < SS_ITEMS; ++c) {
-			s_k[ss_at(base + c)] = v[c].k;
-			if constexpr (WIDE) s_tag[ss_at(base + c)] = v[c].tag;
-		}
-		__syncthreads();
-	}
+	CLO_TS_SORT(WIDE, v, s_k, s_tag, tid, base);
 
 	// position j of the tile holds a row of the segment row j belonged to: a long segment with an odd number of moves
 	// ahead goes to the workspace copy, everything else to the outputs
@@ -286,10 +209,10 @@ void clo_segsort_tile_kernel(const TC* __restrict__ src, const ss_u64* __restric
 		if (j >= t.cnt) continue;
 		const unsigned g = t.tile0 + j;
 		const bool ws = (a_ws && g >= t.A.s && g < t.A.e) || (b_ws && g >= t.B.s && g < t.B.e);
-		const ss_u64 k = s_k[ss_at(j)];
+		const ss_u64 k = s_k[clo_ts_at(j)];
 		unsigned row;
 		TK key;
-		if constexpr (WIDE) { row = s_tag[ss_at(j)] & 0xffffu; key = clo_keyx_inv<TK>((TK) k, kx); }
+		if constexpr (WIDE) { row = s_tag[clo_ts_at(j)] & 0xffffu; key = clo_keyx_inv<TK>((TK) k, kx); }
 		else { row = (unsigned) k & 0xffffu; key = clo_keyx_inv<TK>((TK) (k >> 16), kx); }
 		row = clo_op_min(row, t.cnt - 1u);   // (it is below cnt already: the padding sorts behind)
 		(ws ? kws : kout)[g] = key;

@@ -25,6 +25,7 @@
 #include "clo_bucket.h"
 #include "clo_segarg.h"
 #include "clo_join.h"
+#include "clo_segtopk.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

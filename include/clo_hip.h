@@ -647,6 +647,47 @@ int clo_hip_segarg(int op, int tie, int form, const void* counts_or_offsets, int
 	uint32_t* idx_out, void* val_out, uint64_t* num_out, size_t numel_seg, size_t numel, int value_type,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the k smallest or largest rows of every segment (new functionality: CloSegTopK, include/clo_segtopk.h) ----
+ * m = min(numel_seg, *num_in), the forms (CLO_HIP_SEGTOPK_COUNTS, CLO_HIP_SEGTOPK_OFFSETS), the inclusive ends e_r,
+ * count_size and num_out = e_(m-1) unclamped are clo_hip_expand's above; key_type, value_size and the arg form
+ * (value_size 4, values_in NULL, keys_out optional) are clo_hip_segsort's. With n = numel rows, e_(-1) = 0 and x(i) the
+ * order key of keys_in[i] (complemented for CLO_HIP_SEGTOPK_LARGEST), for every r < m: counts_out[r] = c_r = min(k, the
+ * rows of [min(e_(r-1), n), min(e_r, n))), and keys_out[r * k + j], values_out[r * k + j] for j < c_r are the range's
+ * j-th row in the stable sort by x: ascending x, equal x by ascending row. Keys keep their bits; the arg form writes
+ * the global row as uint. Slots j >= c_r, rows r >= m and counts_out[r >= m] are not written. k is a host argument.
+ * CLO_HIP_EARGS: a which or form that is none of the numbers below, numel_seg or numel >= 2^32, k above
+ * clo_hip_segtopk_k_max, numel_seg * k >= 2^32, clo_hip_segsort's missing pointers, counts_out NULL with numel_seg > 0
+ * and k > 0, num_out NULL or misaligned, num_in misaligned, a pointer not aligned to its element, a missing or
+ * misaligned workspace with numel_seg > 0. Key types, value and count sizes not built: CLO_HIP_EUNSUPPORTED. A
+ * workspace below clo_hip_segtopk_workspace_bytes(numel_seg, numel, k, key_size, value_size): CLO_HIP_EWORKSPACE. No
+ * output may overlap an input, num_in or another output (not checked here: the driver does). numel_seg 0 needs no
+ * workspace and writes *num_out = 0 alone; k 0 writes num_out alone. Whatever the arrays hold, reads stay inside the
+ * inputs, writes inside [0, numel_seg * k) of keys_out and values_out, counts_out[0, numel_seg) and num_out, and the
+ * call completes.
+ * The workspace holds the segment ends of the counts form, a byte and a segment number per row, 32 bytes per tile and
+ * per tile two candidate lists of k (order key, row) pairs.
+ * Launches: for the counts form the three of clo_hip_expand that write the ends; a memset of the row bytes; one thread
+ * per segment and per tile that marks and numbers the first row of every non-empty segment, writes counts_out, num_out
+ * and the tile's two boundary segments; one work-group per tile of clo_hip_segtopk_tile rows that sorts them on chip by
+ * (segment, x, row) — clo_hip_segsort's network — and writes the first k of every segment inside the tile to the
+ * outputs and of the two that cross its boundaries to the candidate lists; ceil(log2(tiles)) combine levels, one
+ * work-group per tile, each of which leaves at once unless a list of its tile takes in the list 2^level tiles further
+ * on. No work-group waits for another and there are no global atomics; asynchronous on `stream`; nothing is allocated
+ * and the host never waits, so the call can be captured into a graph.
+ * clo_hip_segtopk_tile: T, clo_hip_segtopk_k_max: the largest k (T / 2); both 0 for sizes not built.
+ * clo_hip_segtopk_workspace_bytes is monotone in the two counts and in k, 0 for (0, 0, ., ., .) and a multiple of
+ * CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_SEGTOPK_SMALLEST 0
+#define CLO_HIP_SEGTOPK_LARGEST 1
+#define CLO_HIP_SEGTOPK_COUNTS 0
+#define CLO_HIP_SEGTOPK_OFFSETS 1
+size_t clo_hip_segtopk_tile(int key_size, int value_size);
+size_t clo_hip_segtopk_k_max(int key_size, int value_size);
+size_t clo_hip_segtopk_workspace_bytes(size_t numel_seg, size_t numel, size_t k, int key_size, int value_size);
+int clo_hip_segtopk(int which, int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* keys_in, const void* values_in,
+	void* keys_out, void* values_out, uint32_t* counts_out, uint64_t* num_out, size_t numel_seg, size_t numel, size_t k, int key_type, int value_size,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----

@@ -57,7 +57,7 @@
  * contents are then unspecified.
  *
  * Out of scope: half and narrower value types, get_key expressions, several value columns per
- * call, a segment-relative index, the k smallest per segment, numel >= 2^32.
+ * call, a segment-relative index, the k smallest per segment (see clo_segtopk.h), numel >= 2^32.
  */
 #ifndef CLO_SEGARG_H
 #define CLO_SEGARG_H

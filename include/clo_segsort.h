@@ -46,7 +46,7 @@
  * the call completes; the contents are then unspecified.
  *
  * Out of scope: descending order, get_key / run-time comparisons, numel >= 2^32, values wider than
- * 8 bytes, the k smallest per segment.
+ * 8 bytes, the k smallest per segment (see clo_segtopk.h).
  */
 #ifndef CLO_SEGSORT_H
 #define CLO_SEGSORT_H

@@ -50,7 +50,7 @@
  * call completes.
  *
  * Out of scope: sorted output above the cap, numel >= 2^32, a key field inside a wider element
- * (get_key), k per segment, k read from device memory.
+ * (get_key), k per segment (see clo_segtopk.h), k read from device memory.
  */
 #ifndef CLO_TOPK_H
 #define CLO_TOPK_H
