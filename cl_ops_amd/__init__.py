@@ -1,4 +1,4 @@
-"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/join/selection/top-k/expansion/segmented-reduction/segmented-sort/segmented-scan/bucket-partition/segmented-arg-min-max/segmented-top-k primitives and device RNGs behind the cl_ops C API.
+"""cl_ops_amd — MI355X-native sort/scan/reduce-by-key/scan-by-key/histogram/merge/search/set-operation/join/selection/top-k/expansion/segmented-reduction/segmented-sort/segmented-scan/bucket-partition/segmented-arg-min-max/segmented-top-k/segmented-float-sum primitives and device RNGs behind the cl_ops C API.
 
 The product is cl_ops_amd/lib/libcl_ops_hip.so (C-ABI, see include/): host
 drivers in C (cl_ops_amd/csrc) + hand-written HIP kernels for gfx950
@@ -25,6 +25,7 @@ from .segscan import SegScan, segscan_tile, SEGSCAN_OPS, SEGSCAN_FORMS  # noqa: 
 from .bucket import Bucket, bucket_tile, BUCKET_MAX_BINS, BUCKET_SCAN_GROUP, BUCKET_SCAN_TRIP  # noqa: F401
 from .segarg import SegArg, segarg_tile, segarg_carry_tiles, SEGARG_OPS, SEGARG_TIES, SEGARG_NONE  # noqa: F401
 from .segtopk import SegTopK, segtopk_tile, segtopk_k_max, SEGTOPK_WHICH  # noqa: F401
+from .segfsum import SegFSum, segfsum_tile, SEGFSUM_PAIRS  # noqa: F401
 from .topk import TopK, topk_tile, topk_sweep_groups, topk_sorted_max, TOPK_WHICH, TOPK_ORDERS  # noqa: F401
 
 __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profiler", "HipEventTimer",
@@ -40,4 +41,5 @@ __all__ = ["CloError", "Context", "Queue", "Buffer", "Sorter", "Scanner", "Profi
            "Bucket", "bucket_tile", "BUCKET_MAX_BINS", "BUCKET_SCAN_GROUP", "BUCKET_SCAN_TRIP",
            "SegArg", "segarg_tile", "segarg_carry_tiles", "SEGARG_OPS", "SEGARG_TIES", "SEGARG_NONE",
            "SegTopK", "segtopk_tile", "segtopk_k_max", "SEGTOPK_WHICH",
+           "SegFSum", "segfsum_tile", "SEGFSUM_PAIRS",
            "CLO_TYPES", "clo_type", "wait_for_events"]

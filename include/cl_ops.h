@@ -26,6 +26,7 @@
 #include "clo_segarg.h"
 #include "clo_join.h"
 #include "clo_segtopk.h"
+#include "clo_segfsum.h"
 #include "clo_hip.h"
 #include "clo_shard.h"
 

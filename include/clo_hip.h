@@ -688,6 +688,35 @@ int clo_hip_segtopk(int which, int form, const void* counts_or_offsets, int coun
 	void* keys_out, void* values_out, uint32_t* counts_out, uint64_t* num_out, size_t numel_seg, size_t numel, size_t k, int key_type, int value_size,
 	void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- floating-point sums per segment in a fixed order (new functionality: CloSegFSum, include/clo_segfsum.h) ----
+ * m = min(numel_seg, *num_in), the forms (CLO_HIP_SEGFSUM_COUNTS, CLO_HIP_SEGFSUM_OFFSETS), the inclusive ends e_r,
+ * count_size and num_out = e_(m-1) unclamped are clo_hip_expand's above. value_type and sum_type are CloType numbers,
+ * one of the pairs half -> float, float -> float, float -> double, double -> double. With n = numel rows of values_in
+ * and e_(-1) = 0, for every r < m: sums_out[r] = the sum over i in [min(e_(r-1), n), min(e_r, n)) of (sum type)
+ * values_in[i], +0 where that range is empty; every addition is one IEEE addition in the sum type, in the order
+ * include/clo_segfsum.h states, which m, n and the clipped ends alone determine. Rows r >= m are not written.
+ * CLO_HIP_EARGS: a form that is neither number below, numel_seg or numel >= 2^32, counts_or_offsets NULL with
+ * numel_seg > 0 (offsets: always), values_in NULL with numel > 0, sums_out NULL with numel_seg > 0, num_out NULL or
+ * misaligned, num_in misaligned, a pointer not aligned to its element, a missing or misaligned workspace with
+ * numel_seg > 0. Type pairs and count sizes not built: CLO_HIP_EUNSUPPORTED. A workspace below
+ * clo_hip_segfsum_workspace_bytes(numel_seg, numel): CLO_HIP_EWORKSPACE. Neither output may overlap an input, num_in
+ * or the other output (not checked here: the driver does). numel_seg 0 needs no workspace and writes *num_out = 0 alone.
+ * Whatever the arrays hold, reads stay inside the inputs, writes inside sums_out[0, numel_seg) and num_out, and the
+ * call completes.
+ * Launches: clo_hip_segreduce's five stages with a floating-point aggregate that crosses lanes and lies in the
+ * workspace as its bits. values_in is read once. No work-group waits for another and there are no global atomics;
+ * asynchronous on `stream`; nothing is allocated and the host never waits, so the call can be captured into a graph.
+ * clo_hip_segfsum_tile: T = 4352 merge steps for the four pairs' sizes (2, 4), (4, 4), (4, 8), (8, 8), 0 otherwise.
+ * clo_hip_segfsum_workspace_bytes is monotone in both arguments, 0 for (0, 0) and a multiple of
+ * CLO_HIP_WORKSPACE_ALIGN. */
+#define CLO_HIP_SEGFSUM_COUNTS 0
+#define CLO_HIP_SEGFSUM_OFFSETS 1
+size_t clo_hip_segfsum_tile(int value_size, int sum_size);
+size_t clo_hip_segfsum_workspace_bytes(size_t numel_seg, size_t numel);
+int clo_hip_segfsum(int form, const void* counts_or_offsets, int count_size, const uint64_t* num_in, const void* values_in,
+	void* sums_out, uint64_t* num_out, size_t numel_seg, size_t numel, int value_type, int sum_type,
+	void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- LSD radix sort (replaces the per-digit loop of
  *      sort/clo_sort_satradix.c:264-313: satradix_localsort, satradix_histogram,
  *      clo_scan_with_device_data, satradix_scatter — sort/clo_sort_satradix.cl:34-258) ----

@@ -29,6 +29,7 @@
  *
  * Values are int, uint, long or ulong; the sum type is one of the same four and at least as wide as the value type.
  * Floating-point aggregates stay out, for the reason clo_reduce.h gives: their sums depend on the order of addition.
+ * (Floating-point sums per segment, with that order as their contract: CloSegFSum, clo_segfsum.h.)
  *
  * Refused with CLO_ERROR_ARGS before any device call (err may be NULL, the context may be offline; nothing is written):
  * an unknown op or form; options other than NULL or ""; a value or sum type outside the four, a sum type narrower than
